@@ -9,6 +9,10 @@ integer sum is mod 2^64, not mod p).  Reports are distinct, honest, seed-derived
 generated on the device before timing (inputs resident in HBM when the timed region starts).
 
 Usage: python bench.py [--gpus N --steps K --warmup W]  (N>1 via torch.distributed.run)
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR
+also writes what the last timed step computed.  --full adds the roofline pass, the CPU
+restatement baseline with its parity checks and the secondary lines (the other configs and the
+jobs lines) as extra keys of the line.
 """
 from __future__ import annotations
 
@@ -181,6 +185,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reports", type=int, default=1 << 20, help="reports per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="helper role: after the timed steps also run the roofline pass (the "
+                         "per-kernel table of whole-batch launches), the CPU restatement baseline "
+                         "with its GPU parity checks, and the secondary lines; a plain run sets "
+                         "up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="helper role: write what the last timed step computed (prepare messages "
+                         "and statuses of a fixed seeded sample of reports, the aggregate share, "
+                         "count, checksum and interval) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--role", choices=["helper", "leader", "hpke", "pipeline", "mp64", "fpvec", "config",
@@ -237,7 +250,7 @@ def main():
                     help="engine option key=value (e.g. chunks=3, force_generic_query=1), for A/B runs")
     ap.add_argument("--no-secondary", action="store_true",
                     help="helper role, N=1: skip the secondary lines (C1/C3/C4 configs and a short "
-                         "jobs line) that the default run adds as extra keys")
+                         "jobs line) that a --full run adds as extra keys")
     ap.add_argument("--secondary-cpu-seconds", type=float, default=1.5,
                     help="CPU restatement sample size (seconds) for each secondary config line")
     args = ap.parse_args()
@@ -347,16 +360,22 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # Roofline pass (after the timed region): whole-batch launches (option chunks=1, which the
-    # fused k_prep_h default already uses; the two-kernel chain would cut a 1Mi batch into 8
-    # stream-overlapped chunks, where a launch's duration includes its neighbour's share of the
-    # CU), a few steps on the same stream and data.
-    eng.set_option("chunks", 1)
-    eng.timing_reset()
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    times = eng.timing()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, n, prep_msgs, status,
+                     *((combiner.out_agg, combiner.out_cnt, combiner.out_checksums,
+                        combiner.out_intervals) if combiner is not None else (agg, cnt, cks, ivs)))
+    times = None
+    if args.full:
+        # Roofline pass (after the timed region): whole-batch launches (option chunks=1, which
+        # the fused k_prep_h default already uses; the two-kernel chain would cut a 1Mi batch
+        # into 8 stream-overlapped chunks, where a launch's duration includes its neighbour's
+        # share of the CU), a few steps on the same stream and data.
+        eng.set_option("chunks", 1)
+        eng.timing_reset()
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        times = eng.timing()
     eng.set_option("timing", 0)
     eng.set_option("chunks", chunks_opt)
 
@@ -364,6 +383,95 @@ def main():
     final_cnt = int((combiner.out_cnt if combiner is not None else cnt)[0].item())
     value = world * n * args.steps / elapsed
 
+    out = dict(metric=METRIC, value=value, unit="reports/s", n_gpus=world, steps=args.steps,
+               warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
+               higher_is_better=True, scaling="weak", vs_baseline=None,
+               dtype="u32 limbs (Field128 mod-p integer arithmetic)",
+               data="synthetic: distinct honest reports generated on-device from a seed "
+                    "(client shard + leader prepare_init); verify key fixed",
+               config=dict(workload="Prio3Histogram length=256 chunk_length=16 helper "
+                                    "prepare_init+prepare_shares_to_prepare_message+prepare_next"
+                                    "+aggregate, 1 segment",
+                           reports_per_gpu=n, global_batch=world * n,
+                           parallelism=f"dp{world} (report shards; RCCL all-gather + mod-p combine)"))
+    if times is not None:
+        out.update(headline_roofline(times, n, args.steps, elapsed))
+    out.update(kernels_timed_region={k: dict(ms_total=v[0], launches=v[1])
+                                     for k, v in step_times.items()},
+               checks=dict(finished=ok, generator_flags=flags, agg_count=final_cnt))
+    if world > 1:
+        out["dist_backend"] = args.dist_backend
+        if args.dist_backend == "gloo":
+            out["note"] = "gloo: all-gather staged through host memory (a correctness run, not RCCL)"
+    if world > 1 and args.check_combined and rank == 0:
+        out["checks"]["combined_matches_oracle"] = check_combined(eng, args, world, n, times_of,
+                                                                  combiner)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
+        cb, (msgs, cst, cagg, ccnt) = cpu_baseline(eng, data, min(n, 1 << 20), args.cpu_seconds)
+        m = cb.pop("n")
+        gm = prep_msgs[:m].cpu().numpy()
+        gs = status[:m].cpu().numpy()
+        # the GPU aggregate share and count of the same sample: the last step's device run
+        # finished again with an accept mask selecting its first m reports
+        accept = torch.zeros(n, dtype=torch.uint8, device=dev)
+        accept[:m] = 1
+        agg_s = torch.zeros_like(agg)
+        cnt_s = torch.zeros_like(cnt)
+        eng.aggregate_finish_device(status, accept, agg_s, cnt_s)
+        torch.cuda.synchronize()
+        out["checks"]["cpu_gpu_parity_on_sample"] = bool(
+            np.array_equal(gs, cst) and np.array_equal(gm, msgs) and
+            np.array_equal(agg_s.cpu().numpy().reshape(-1), np.asarray(cagg).reshape(-1)) and
+            int(cnt_s[0].item()) == int(np.asarray(ccnt).reshape(-1)[0]))
+        out["checks"]["cpu_gpu_parity_covers"] = (f"statuses, prepare messages, aggregate share "
+                                                  f"and count of {m} reports")
+        from oracle.oracle import batch_metadata
+        eck, eiv = batch_metadata(data["nonces"].cpu().numpy(), report_times.cpu().numpy(),
+                                  status.cpu().numpy(), None, None, 1)
+        out["checks"]["batch_metadata_parity"] = bool(
+            np.array_equal(cks.cpu().numpy(), eck) and
+            np.array_equal(ivs.cpu().numpy().view(np.uint64), eiv))
+        out["cpu_baseline"] = cb
+        out["speedup_vs_cpu"] = value / cb["value"]
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
+        del data, prep_msgs, status, seg, report_times
+        eng.close()
+        torch.cuda.empty_cache()
+        out.update(secondary_lines(args))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 16  # reports whose prepare message and status --dump-outputs keeps
+
+
+def dump_outputs(path: str, n: int, prep_msgs, status, agg, cnt, cks, ivs) -> None:
+    """--dump-outputs: the arrays a caller of the timed step receives, as float .npy files (every
+    value is a byte, a count or a time in seconds, so float32 / float64 hold them exactly).  The
+    per-report outputs are kept for a fixed seeded sample of DUMP_SAMPLE reports (all of them for
+    a smaller batch; 1 Mi prepare messages alone are 64 MiB as float32); `sample_index` names
+    them.  The per-batch outputs are whole."""
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0x4A414E55).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    sel = torch.from_numpy(idx).to(status.device)
+    arrays = dict(sample_index=idx.astype(np.float64),
+                  prep_msgs=prep_msgs[sel].cpu().numpy().astype(np.float32),
+                  status=status[sel].cpu().numpy().astype(np.float32),
+                  aggregate_share=agg.cpu().numpy().astype(np.float32),
+                  count=cnt.cpu().numpy().astype(np.float64),
+                  checksum=cks.cpu().numpy().astype(np.float32),
+                  interval=ivs.cpu().numpy().astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def headline_roofline(times: dict, n: int, steps: int, elapsed: float) -> dict:
+    """The headline's `roofline` and `kernels` keys from the roofline pass's per-kernel times."""
     # roofline of the dominant kernel, from the live HIP-event times on the launch stream:
     # achieved = the frozen gfx950 VALU model (valu_model, DESIGN.md 3) x reports / duration;
     # the measured instructions per report (PMC SQ_INSTS_VALU / SQ_WAVES, profiles/) give the
@@ -407,8 +515,8 @@ def main():
                     frac_of_measured_issue=d["model_T"] / MEASURED_ISSUE_T,
                     hbm_algorithmic_GBps=d.get("hbm_algorithmic_GBps"), hbm_peak_GBps=PEAK_HBM / 1e9,
                     step=dict(model_instr_per_report=step_model,
-                              achieved=step_model * n * args.steps / elapsed / 1e12,
-                              frac=step_model * n * args.steps / elapsed / 1e12 / peak_T,
+                              achieved=step_model * n * steps / elapsed / 1e12,
+                              frac=step_model * n * steps / elapsed / 1e12 / peak_T,
                               note="whole timed step (all kernels), per GPU"))
     qk = next((k for k in ("k_query_rows", "k_query_h", "k_query_pair") if k in per_kernel), None)
     qh = per_kernel.get(qk) if qk else None
@@ -417,67 +525,11 @@ def main():
                                      achieved_TBps=qh["hbm_pmc_TBps"], peak_TBps=PEAK_HBM / 1e12,
                                      frac=qh["hbm_frac"])
 
-    out = dict(metric=METRIC, value=value, unit="reports/s", n_gpus=world, steps=args.steps,
-               warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
-               higher_is_better=True, scaling="weak", vs_baseline=None,
-               dtype="u32 limbs (Field128 mod-p integer arithmetic)",
-               data="synthetic: distinct honest reports generated on-device from a seed "
-                    "(client shard + leader prepare_init); verify key fixed",
-               config=dict(workload="Prio3Histogram length=256 chunk_length=16 helper "
-                                    "prepare_init+prepare_shares_to_prepare_message+prepare_next"
-                                    "+aggregate, 1 segment",
-                           reports_per_gpu=n, global_batch=world * n,
-                           parallelism=f"dp{world} (report shards; RCCL all-gather + mod-p combine)"),
-               roofline=roofline, kernels=per_kernel,
-               kernels_timed_region={k: dict(ms_total=v[0], launches=v[1]) for k, v in step_times.items()},
-               checks=dict(finished=ok, generator_flags=flags, agg_count=final_cnt))
-    if world > 1:
-        out["dist_backend"] = args.dist_backend
-        if args.dist_backend == "gloo":
-            out["note"] = "gloo: all-gather staged through host memory (a correctness run, not RCCL)"
-    if world > 1 and args.check_combined and rank == 0:
-        out["checks"]["combined_matches_oracle"] = check_combined(eng, args, world, n, times_of,
-                                                                  combiner)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cb, (msgs, cst, cagg, ccnt) = cpu_baseline(eng, data, min(n, 1 << 20), args.cpu_seconds)
-        m = cb.pop("n")
-        gm = prep_msgs[:m].cpu().numpy()
-        gs = status[:m].cpu().numpy()
-        # the GPU aggregate share and count of the same sample: the last step's device run
-        # finished again with an accept mask selecting its first m reports
-        accept = torch.zeros(n, dtype=torch.uint8, device=dev)
-        accept[:m] = 1
-        agg_s = torch.zeros_like(agg)
-        cnt_s = torch.zeros_like(cnt)
-        eng.aggregate_finish_device(status, accept, agg_s, cnt_s)
-        torch.cuda.synchronize()
-        out["checks"]["cpu_gpu_parity_on_sample"] = bool(
-            np.array_equal(gs, cst) and np.array_equal(gm, msgs) and
-            np.array_equal(agg_s.cpu().numpy().reshape(-1), np.asarray(cagg).reshape(-1)) and
-            int(cnt_s[0].item()) == int(np.asarray(ccnt).reshape(-1)[0]))
-        out["checks"]["cpu_gpu_parity_covers"] = (f"statuses, prepare messages, aggregate share "
-                                                  f"and count of {m} reports")
-        from oracle.oracle import batch_metadata
-        eck, eiv = batch_metadata(data["nonces"].cpu().numpy(), report_times.cpu().numpy(),
-                                  status.cpu().numpy(), None, None, 1)
-        out["checks"]["batch_metadata_parity"] = bool(
-            np.array_equal(cks.cpu().numpy(), eck) and
-            np.array_equal(ivs.cpu().numpy().view(np.uint64), eiv))
-        out["cpu_baseline"] = cb
-        out["speedup_vs_cpu"] = value / cb["value"]
-    if rank == 0 and world == 1 and not args.no_secondary:
-        del data, prep_msgs, status, seg, report_times
-        eng.close()
-        torch.cuda.empty_cache()
-        out.update(secondary_lines(args))
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.destroy_process_group()
+    return dict(roofline=roofline, kernels=per_kernel)
 
 
 def _summary(d: dict) -> dict:
-    """The fields of a secondary line the default bench keeps (the full line is what --role
+    """The fields of a secondary line the --full bench keeps (the whole line is what --role
     config / --role jobs print)."""
     rf = d.get("roofline") or {}
     cb = d.get("cpu_baseline") or {}

@@ -14,7 +14,7 @@ unset JANUS_PRIO3_LIB
 one() {  # LIB TAG ARGS
   local lib=$1 tag=$2; shift 2
   if [ "$lib" = base ]; then unset JANUS_PRIO3_LIB; else export JANUS_PRIO3_LIB=$PWD/janus_amd/variants/libjanus_prio3_$lib.so; fi
-  timeout -k 10 180 python3 bench.py --no-cpu-baseline --no-secondary --warmup 5 --steps 40 "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { tail -20 "$OUT/$tag.err"; exit 1; }
+  timeout -k 10 180 python3 bench.py --full --no-cpu-baseline --no-secondary --warmup 5 --steps 40 "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { tail -20 "$OUT/$tag.err"; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/$tag.json')); print('$tag', round(d['value']/1e6,2), {k: round(v['ms_avg'],3) for k,v in d['kernels'].items() if v['ms_avg']>0.05}, d['checks'])"
 }

@@ -64,7 +64,7 @@ for step in "$@"; do
   bench)
     bench "$a1" $(args "$a2") ;;
   lines)
-    bench c2
+    bench c2 --full
     bench c1 --role config --vdaf count
     bench c3 --role config --vdaf sumvec
     bench c4 --role config --vdaf sum32

@@ -5,7 +5,7 @@
 set -e
 TAG=$1; shift
 R=$(pwd); OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-B="$R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --opt chunks=1 $@"
+B="$R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --opt chunks=1 $@"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $B > $OUT/bench.json
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o run -- python3 $B > /dev/null
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o run -- python3 $B > /dev/null
