@@ -84,7 +84,7 @@ void janus_hpke_opener_destroy(janus_hpke_opener* opener);
  *   d_enc[r][Nenc]                    HpkeCiphertext.encapsulated_key (Nenc of the KEM, above)
  *   d_ct[r][ct_stride], d_ct_len[r]   HpkeCiphertext.payload (ciphertext || 16-byte tag)
  *   d_report_ids[r][16], d_times[r]   ReportMetadata (report ID, time in seconds)
- *   d_public_shares[r][public_share_len]
+ *   d_public_shares[r][public_share_len]   (0, 32 or 64 bytes; else JANUS_HPKE_EINVAL)
  * The AAD is InputShareAad { task_id, metadata, public_share } (messages/src/lib.rs:1825-1872),
  * built on the device.  Output: d_helper_shares[r][helper_share_len] (zeroed unless status OK)
  * and d_status[r].  require_taskprov: the task is a taskprov task (aggregator.rs:1925-1958). */

@@ -62,13 +62,16 @@ enum {
                                           InvalidMessage (aggregation_job_driver.rs:397-415) */
 };
 
-/* Merged per-report status of prio3_helper_aggregate_init_batch for a report the helper rejects
- * before its VDAF runs: 0x80 | the DAP PrepareError Janus records (messages/src/lib.rs
- * PrepareError; aggregator.rs:1847-1983), which takes precedence over any VDAF status. */
+/* Merged per-report status of prio3_helper_aggregate_init_batch[_ex] for a report the helper
+ * rejects before its VDAF runs: 0x80 | the DAP PrepareError Janus records (messages/src/lib.rs
+ * PrepareError; aggregator.rs:1847-2015), which takes precedence over any VDAF status.  Among
+ * themselves they take the order of aggregator.rs: the open and decode (0x84 / 0x88) first, then
+ * the report deadline (0x89). */
 enum {
   PRIO3_STATUS_HPKE_DECRYPT = 0x84,     /* PrepareError::HpkeDecryptError (open / AAD failed) */
   PRIO3_STATUS_INVALID_MESSAGE = 0x88,  /* PrepareError::InvalidMessage (PlaintextInputShare,
                                            extensions, helper input share length) */
+  PRIO3_STATUS_REPORT_TOO_EARLY = 0x89, /* PrepareError::ReportTooEarly (time after the deadline) */
 };
 
 /* Whole-call return codes. */
@@ -215,11 +218,40 @@ int prio3_helper_prepare_aggregate_batch(prio3_engine* engine, uint32_t n, const
  * prio3_accumulate.  status_out[n]: PRIO3_STATUS_* of the report's VDAF, or
  * PRIO3_STATUS_HPKE_DECRYPT / PRIO3_STATUS_INVALID_MESSAGE when the open rejected it (such a
  * report is never counted).  Instances whose public share is neither 0 nor 32 bytes
- * (PRIO3_SUMVEC_F64_MP) return PRIO3_EUNSUPPORTED.  The opener may be bound to any GPU: the open
- * runs on the GPU the job is placed on. */
+ * (PRIO3_SUMVEC_F64_MP) return PRIO3_EUNSUPPORTED here; the _ex form below takes them.  The opener
+ * may be bound to any GPU: the open runs on the GPU the job is placed on.
+ * This is prio3_helper_aggregate_init_batch_ex without a fallback keypair and without a report
+ * deadline. */
 struct janus_hpke_opener;
 int prio3_helper_aggregate_init_batch(
     prio3_engine* engine, struct janus_hpke_opener* opener, uint32_t n,
+    const uint8_t task_id[32], int require_taskprov, const uint8_t* report_ids,
+    const uint64_t* times, const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct,
+    const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* leader_prep_shares,
+    const uint32_t* segment_ids, const uint8_t* accept_mask, uint32_t n_segments,
+    uint8_t* prep_msgs_out, uint8_t* status_out, uint8_t* agg_shares_out, uint64_t* counts_out);
+
+/* The same call with the whole status contract of the loop body, still ONE coalesced group launch
+ * (jobs also share it only with jobs of the same fallback keypair, or likewise none):
+ *  - opener is the keypair tried first: the task's keypair for the reports' config id, or the
+ *    global one when the task has none.  fallback_opener (NULL: none) is the global keypair when
+ *    both exist (aggregator.rs:1864-1878): a report whose open under `opener` ends in
+ *    HpkeDecryptError -- and only such a report; one that opened and then failed its decode or
+ *    extension checks keeps 0x88 -- is opened again under fallback_opener inside the launch, and
+ *    that plaintext passes the same decode and checks (so it ends in 0, 0x84 or 0x88).  Both
+ *    openers must be of the same KEM (one enc[n][Nenc] layout), else PRIO3_EINVAL; a NULL opener is
+ *    PRIO3_EINVAL.  A config id no keypair is known for (HpkeUnknownConfigId) stays with the
+ *    caller: no keypair, no call.
+ *  - report_deadline (seconds; UINT64_MAX: no check): a report with times[i] > report_deadline gets
+ *    PRIO3_STATUS_REPORT_TOO_EARLY (aggregator.rs:2004-2015; a time equal to the deadline passes).
+ *    Precedence: PRIO3_STATUS_HPKE_DECRYPT / _INVALID_MESSAGE, then _REPORT_TOO_EARLY, then the
+ *    VDAF status.  Such a report is never counted and its prepare message is undefined, as for
+ *    the open's rejections.  Concurrent jobs of one task may carry different deadlines.
+ *  - every instance is admitted, PRIO3_SUMVEC_F64_MP included (64-byte public shares, 96-byte
+ *    helper shares, 32-byte prepare messages). */
+int prio3_helper_aggregate_init_batch_ex(
+    prio3_engine* engine, struct janus_hpke_opener* opener,
+    struct janus_hpke_opener* fallback_opener, uint64_t report_deadline, uint32_t n,
     const uint8_t task_id[32], int require_taskprov, const uint8_t* report_ids,
     const uint64_t* times, const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct,
     const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* leader_prep_shares,

@@ -13,6 +13,7 @@
 // instruction stream (no key-dependent branch).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -687,6 +688,10 @@ struct OpenArgs {
   // (BE words, like HpkeParams::task); nullable: HpkeParams::task
   const uint16_t* task_slot;
   const uint32_t* task_tab;
+  // retry pass of a sealed-input group: lane q opens report idx[q], q < min(*n_idx, n) (both in
+  // device memory, written on the launch's stream); nullable: lane q opens report q < n
+  const uint32_t* idx;
+  const uint32_t* n_idx;
 };
 
 // word i of report r's task ID (input-share AAD), BE
@@ -894,13 +899,19 @@ __global__ __launch_bounds__(256) HPKE_WAVES void k_hpke_open(HpkeParams P, Open
   static_assert(KEM == 0x20 || KEM == 0x10 || KEM == 0x21 || KEM == 0x12 || KEM == 0x11, "KEM id");
   static_assert(!PAIR || KEM == 0x20, "the lane-pair ladder is X25519's");
   const uint32_t AEAD = P.aead;
+  // PAIR: two lanes per report; they differ only inside the ladder and write the same bytes
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t q = PAIR ? gid >> 1 : gid;
+  uint32_t lim = a.n;
+  if (a.idx) {  // a listed launch's grid covers n: the blocks past the list leave at once
+    lim = min(*a.n_idx, a.n);
+    if ((PAIR ? (blockIdx.x * blockDim.x) >> 1 : blockIdx.x * blockDim.x) >= lim) return;
+  }
   __shared__ AesT T;
   aes_tables_init(T);
   __syncthreads();
-  // PAIR: two lanes per report; they differ only inside the ladder and write the same bytes
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t r = PAIR ? gid >> 1 : gid;
-  if (r >= a.n) return;
+  if (q >= lim) return;
+  const uint32_t r = a.idx ? a.idx[q] : q;
   // ---- DHKEM Decap (RFC 9180 4.1): dh, then ExtractAndExpand(dh, enc || pkRm) -------------
   constexpr int NSS = KemC<KEM>::NSS_W;
   uint32_t ss[NSS], keyw[8], noncew[3];
@@ -1487,13 +1498,15 @@ static void recode_w4(const uint32_t* sk, const uint32_t* n, int nw, int ndig, i
 struct janus_hpke_opener {
   int device = 0;
   int coalesce = 1;  // host-buffer opens through the executor (janus_hpke_executor_control)
-  int pair_max = JANUS_HPKE_PAIR_MAX;  // lane-pair ladder for opens of at most this many reports
+  // lane-pair ladder for opens of at most this many reports; read by the executors' group keys
+  // without mu, like timing
+  std::atomic<int> pair_max{JANUS_HPKE_PAIR_MAX};
   hipStream_t stream = nullptr;
   HpkeParams P;
   uint8_t* d_pt = nullptr;
   size_t pt_cap = 0;
   std::mutex mu;
-  int timing = 0;
+  std::atomic<int> timing{0};
   double ms = 0;
   uint32_t launches = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -1670,8 +1683,13 @@ int janus_hpke_timing(janus_hpke_opener* o, double* ms_total, uint32_t* launches
 
 }  // extern "C"
 
+// public-share lengths the input-share open takes: none, two 16-byte or two 32-byte seeds
+static bool hpke_pub_len_ok(uint32_t pub) { return pub == 0 || pub == 32 || pub == 64; }
+
 static int launch_open(janus_hpke_opener* o, int mode, int pub, const OpenArgs& a,
                        hipStream_t st) {
+  // MODE 1 builds the InputShareAad for public shares of 0, 32 or 64 bytes (one instance each)
+  if (mode == 1 && !hpke_pub_len_ok((uint32_t)pub)) return JANUS_HPKE_EINVAL;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (o->timing) {
     HCHK(hipEventCreate(&e0));
@@ -1682,6 +1700,8 @@ static int launch_open(janus_hpke_opener* o, int mode, int pub, const OpenArgs& 
 #define JANUS_HPKE_LAUNCH(KE)                                    \
   if (mode == 0)                                                 \
     k_hpke_open<0, 0, KE><<<blocks, 256, 0, st>>>(o->P, a);      \
+  else if (pub == 64)                                            \
+    k_hpke_open<1, 64, KE><<<blocks, 256, 0, st>>>(o->P, a);     \
   else if (pub == 32)                                            \
     k_hpke_open<1, 32, KE><<<blocks, 256, 0, st>>>(o->P, a);     \
   else                                                           \
@@ -1692,7 +1712,9 @@ static int launch_open(janus_hpke_opener* o, int mode, int pub, const OpenArgs& 
                     a.n <= (uint32_t)o->pair_max;
   if (pair) {
     const uint32_t b2 = (2 * a.n + 255) / 256;
-    if (pub == 32)
+    if (pub == 64)
+      k_hpke_open<1, 64, 0x20, true><<<b2, 256, 0, st>>>(o->P, a);
+    else if (pub == 32)
       k_hpke_open<1, 32, 0x20, true><<<b2, 256, 0, st>>>(o->P, a);
     else
       k_hpke_open<1, 0, 0x20, true><<<b2, 256, 0, st>>>(o->P, a);
@@ -1728,6 +1750,7 @@ static int ensure_pt(janus_hpke_opener* o, size_t bytes) {
 // ---- executor hooks (prio3_runtime.h) ----
 int hpke_opener_device(const janus_hpke_opener* o) { return o->device; }
 size_t hpke_opener_nenc(const janus_hpke_opener* o) { return kem_nenc((uint16_t)o->P.kem); }
+uint32_t hpke_opener_kem(const janus_hpke_opener* o) { return o->P.kem; }
 uint64_t hpke_opener_key(const janus_hpke_opener* o) {
   uint64_t h = 1469598103934665603ull;
   auto mix = [&](uint64_t x) { h = (h ^ x) * 1099511628211ull; };
@@ -1755,6 +1778,8 @@ int hpke_open_group_launch(janus_hpke_opener* o, const HpkeGroupArgs& g, hipStre
   a.status = g.status;
   a.task_slot = g.task_slot;
   a.task_tab = g.task_tab;
+  a.idx = g.idx;
+  a.n_idx = g.n_idx;
   std::lock_guard<std::mutex> lk(o->mu);  // o->P and the timing list
   return launch_open(o, 1, (int)g.pub_len, a, st) == JANUS_HPKE_SUCCESS ? PRIO3_OK : PRIO3_EDEVICE;
 }
@@ -1880,7 +1905,7 @@ int janus_hpke_open_input_shares_device(janus_hpke_opener* o, uint32_t n,
   if (n == 0) return JANUS_HPKE_SUCCESS;
   if (!d_enc || !d_ct || !d_ct_len || !d_report_ids || !d_times || !d_helper_shares ||
       !d_status || ct_stride == 0 || ct_stride % 16 != 0 ||
-      (public_share_len != 0 && public_share_len != 32) || (public_share_len && !d_public_shares))
+      !hpke_pub_len_ok(public_share_len) || (public_share_len && !d_public_shares))
     return JANUS_HPKE_EINVAL;
   std::lock_guard<std::mutex> lk(o->mu);
   DeviceGuard dg_(o->device);
@@ -2092,7 +2117,7 @@ int janus_hpke_open_input_shares(janus_hpke_opener* o, uint32_t n, const uint8_t
   if (!o || !task_id) return JANUS_HPKE_EINVAL;
   if (n == 0) return JANUS_HPKE_SUCCESS;
   if (!enc || !ct || !ct_len || !report_ids || !times || !helper_shares || !status ||
-      ct_stride == 0 || ct_stride % 16 != 0 || (public_share_len != 0 && public_share_len != 32) ||
+      ct_stride == 0 || ct_stride % 16 != 0 || !hpke_pub_len_ok(public_share_len) ||
       (public_share_len && !public_shares))
     return JANUS_HPKE_EINVAL;
   if (o->coalesce) {  // concurrent jobs of every task on this keypair: one launch (exec_hpke)

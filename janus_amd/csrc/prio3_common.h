@@ -643,6 +643,9 @@ struct Run {
   // sealed-input groups (RUN_HPKE): the open's status per report and its plaintext scratch
   uint32_t hpke_stride = 0;
   uint8_t *hstatus = nullptr, *hpt = nullptr;
+  // the retry pass of a group with a fallback keypair: [0] the count, [1 .. n] the reports to open
+  // again (k_hpke_retry_list)
+  uint32_t* hretry = nullptr;
 };
 
 struct prio3_engine {

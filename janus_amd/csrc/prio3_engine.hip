@@ -3033,6 +3033,7 @@ static size_t run_carve(Run* R, unsigned flags, uint32_t n_keys, uint8_t* base) 
   if (flags & RUN_HPKE) {
     take(&R->hstatus, n);
     take(&R->hpt, (size_t)R->hpke_stride * n);
+    take(&R->hretry, 4 * (n + 1));
   }
   if (flags & RUN_FUSED) {
     // sized for 32-report waves (k_prep_hp); the one-lane kernels use the first half
@@ -3728,6 +3729,10 @@ uint64_t exec_job_key(const ExecJob* j) {
     const uint64_t u[4] = {0x5345414C4544ull, hpke_opener_key(j->opener), j->ct_stride,
                            (uint64_t)j->require_taskprov};
     h = fnv(h, u, sizeof u);
+    if (j->fallback) {  // and one fallback keypair (jobs without one launch apart: no retry pass)
+      const uint64_t f[2] = {0x46414C4C4241434Bull, hpke_opener_key(j->fallback)};
+      h = fnv(h, f, sizeof f);
+    }
   }
   return h;
 }
@@ -3785,6 +3790,8 @@ void engine_io_layout(const prio3_engine* e, uint32_t cap, IoLayout* L, const Ex
     off += up(2 * (size_t)cap);
     L->ttab_off = off;
     off += 32 * (size_t)HPKE_MAX_TASKS;
+    L->dtab_off = off;
+    off += 8 * (size_t)HPKE_MAX_TASKS;
   }
   L->bytes = off;
 }
@@ -3809,9 +3816,42 @@ static void record_prep(GroupRun* gr, hipStream_t st) {
 // Sealed-input groups: a report the open rejected (HPKE status 4 or 8) gets status 0x80 | that
 // PrepareError, whatever its prepare computed on the zeroed share -- so the accumulate, which
 // counts status 0 only, leaves it out, and the caller sees the error Janus records first.
-__global__ __launch_bounds__(256) void k_hpke_merge(uint32_t n, const uint8_t* hs, uint8_t* status) {
+// Then the report deadline (aggregator.rs:2004-2015, after the open and decode, before the VDAF's
+// status counts): a report the open accepted whose time is after its job's deadline -- the
+// deadline table's entry of its task slot -- gets 0x80 | ReportTooEarly, so it is left out of the
+// accumulate the same way.  times == nullptr: no job of the group carries a deadline.
+__global__ __launch_bounds__(256) void k_hpke_merge(uint32_t n, const uint8_t* hs, uint8_t* status,
+                                                    const uint64_t* times, const uint16_t* tslot,
+                                                    const uint64_t* dtab) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n && hs[i]) status[i] = (uint8_t)(0x80u | hs[i]);
+  if (i >= n) return;
+  if (hs[i])
+    status[i] = (uint8_t)(0x80u | hs[i]);
+  else if (times && times[i] > dtab[tslot[i]])
+    status[i] = (uint8_t)PRIO3_STATUS_REPORT_TOO_EARLY;
+}
+
+// The retry list of a group with a fallback keypair: the reports whose first open ended in
+// HpkeDecryptError (4) and whose ciphertext length is one an open can accept -- the pad columns
+// (length 0) and over- or undersized rows stay 4 under any key, so they cost no second ladder.
+// list[0] is the count (zeroed on the stream before this launch), list[1 ..] the report indices,
+// one atomic per wave; the order is arbitrary, every listed report rewrites its own row only.
+__global__ __launch_bounds__(256) void k_hpke_retry_list(uint32_t n, const uint8_t* hs,
+                                                         const uint32_t* ct_len,
+                                                         uint32_t ct_stride, uint32_t* list) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool q = false;
+  if (i < n && hs[i] == 4) {
+    const uint32_t cl = ct_len[i];
+    q = cl >= 16 && cl <= ct_stride;
+  }
+  const uint64_t m = __ballot(q);
+  if (!m) return;  // wave-uniform
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(list, (uint32_t)__popcll(m));
+  base = (uint32_t)__shfl((int)base, 0);
+  if (q) list[1 + base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
 }
 
 // Group launch (host pull, the r03 form).  The kernels read each report's nonce, public share,
@@ -3884,6 +3924,20 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
     a.shares = R->helper;
     a.status = R->hstatus;
     if (hpke_open_group_launch(g.opener, a, st) != PRIO3_OK) return fail(PRIO3_EDEVICE);
+    if (g.fallback) {
+      // the reports the first keypair could not decrypt, opened again under the fallback keypair
+      // (hpke::Error::Hpke(_) => try_hpke_open(global), aggregator.rs:1864-1878): the list is made
+      // and consumed on the stream, the host never sees it; the second launch covers n lanes and
+      // its blocks past the list leave at once.  It rewrites the listed rows' share, plaintext
+      // and open status, which then pass through the same merge as a first open's.
+      if (hipMemsetAsync(R->hretry, 0, 4, st) != hipSuccess) return fail(PRIO3_EDEVICE);
+      k_hpke_retry_list<<<(g.n + 255) / 256, 256, 0, st>>>(g.n, R->hstatus, a.ct_len, L.ct_stride,
+                                                          R->hretry);
+      if (hipGetLastError() != hipSuccess) return fail(PRIO3_EDEVICE);
+      a.idx = R->hretry + 1;
+      a.n_idx = R->hretry;
+      if (hpke_open_group_launch(g.fallback, a, st) != PRIO3_OK) return fail(PRIO3_EDEVICE);
+    }
     in.helper = R->helper;
     // the executor may issue the next group as soon as this one's open is done: a group's open
     // (one X25519 ladder per lane, ~1 wave per SIMD on half the SIMDs at 31k reports) then runs
@@ -3913,7 +3967,9 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
   if (agg) R->seg = R->gseg;
   if (rc) return fail(rc);
   if (sealed) {  // the open's rejections take precedence (aggregator.rs:1850-1990 before :2020)
-    k_hpke_merge<<<(g.n + 255) / 256, 256, 0, st>>>(g.n, R->hstatus, R->status);
+    k_hpke_merge<<<(g.n + 255) / 256, 256, 0, st>>>(
+        g.n, R->hstatus, R->status, g.deadlines ? (const uint64_t*)(hd + L.time_off) : nullptr,
+        (const uint16_t*)(hd + L.tslot_off), (const uint64_t*)(hd + L.dtab_off));
     if (hipGetLastError() != hipSuccess) return fail(PRIO3_EDEVICE);
   }
   // the executor may issue its next group once this group's prepare kernels are done
@@ -4949,8 +5005,13 @@ int prio3_helper_prepare_aggregate_batch(prio3_engine* e, uint32_t n, const uint
 // group's launch opens every report's input share into HBM, prepares the reports from there and
 // accumulates them per segment; only statuses, prepare messages, aggregate shares and counts come
 // back.  A group too wide for its segments takes the same steps as two host calls.
-int prio3_helper_aggregate_init_batch(
-    prio3_engine* e, janus_hpke_opener* opener, uint32_t n, const uint8_t task_id[32],
+// With the rest of the status contract of aggregator.rs (the _ex form): the task-then-global
+// keypair retry (:1864-1878) as a second open pass inside the group launch, and the report deadline
+// (:2004-2015) applied where the open's rejections are merged, ahead of the accumulate.
+// max_pub: the longest public share the entry point admits (the plain form keeps its 32).
+static int helper_aggregate_init(
+    prio3_engine* e, janus_hpke_opener* opener, janus_hpke_opener* fallback_opener,
+    uint64_t report_deadline, uint32_t max_pub, uint32_t n, const uint8_t task_id[32],
     int require_taskprov, const uint8_t* report_ids, const uint64_t* times,
     const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct, const uint32_t* ct_len,
     uint32_t ct_stride, const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
@@ -4962,11 +5023,16 @@ int prio3_helper_aggregate_init_batch(
       (n && (!report_ids || !times || !enc || !ct || !ct_len || !leader_prep_shares ||
              !status_out)))
     return PRIO3_EINVAL;
+  // one enc[n][Nenc] layout serves both opens
+  if (fallback_opener && hpke_opener_kem(fallback_opener) != hpke_opener_kem(opener))
+    return PRIO3_EINVAL;
   if (e->dp.kind == PRIO3_FPVEC_BOUNDED_L2 && !e->experimental_fpvec)
     return PRIO3_EUNSUPPORTED;  // unpinned reconstruction: explicit opt-in only
   const DevParams& d = e->dp;
-  // the open kernel's AAD takes public shares of 0 or 32 bytes (every TurboSHAKE instance)
-  if (d.public_share_len != 0 && d.public_share_len != 32) return PRIO3_EUNSUPPORTED;
+  // the open kernel's AAD takes public shares of 0, 32 or 64 bytes (every instance there is)
+  if ((d.public_share_len != 0 && d.public_share_len != 32 && d.public_share_len != 64) ||
+      d.public_share_len > max_pub)
+    return PRIO3_EUNSUPPORTED;
   if (n && d.jr_len && (!public_shares || !prep_msgs_out)) return PRIO3_EINVAL;
   const size_t agg_len = (size_t)d.out_len * d.es;
   if (n == 0) {
@@ -4984,14 +5050,55 @@ int prio3_helper_aggregate_init_batch(
                                           d.public_share_len, d.helper_share_len,
                                           require_taskprov, shares.data(), hs.data());
     if (rc) return rc == JANUS_HPKE_EDEVICE ? PRIO3_EDEVICE : PRIO3_EINVAL;
-    for (uint32_t i = 0; i < n; i++) acc[i] = (!accept_mask || accept_mask[i]) && hs[i] == 0;
+    if (fallback_opener) {  // the HpkeDecryptError rows again, under the fallback keypair
+      std::vector<uint32_t> idx;
+      for (uint32_t i = 0; i < n; i++)
+        if (hs[i] == 4 && ct_len[i] >= 16 && ct_len[i] <= ct_stride) idx.push_back(i);
+      const uint32_t m = (uint32_t)idx.size();
+      if (m) {
+        const size_t nenc = hpke_opener_nenc(opener), pl = d.jr_len ? d.public_share_len : 0;
+        std::vector<uint8_t> enc2(nenc * m), ct2((size_t)ct_stride * m), ids2(16 * (size_t)m),
+            pub2(pl * m), sh2((size_t)d.helper_share_len * m), hs2(m);
+        std::vector<uint32_t> cl2(m);
+        std::vector<uint64_t> tm2(m);
+        for (uint32_t k = 0; k < m; k++) {
+          const size_t i = idx[k];
+          memcpy(&enc2[nenc * k], enc + nenc * i, nenc);
+          memcpy(&ct2[(size_t)ct_stride * k], ct + (size_t)ct_stride * i, ct_stride);
+          memcpy(&ids2[16 * (size_t)k], report_ids + 16 * i, 16);
+          if (pl) memcpy(&pub2[pl * k], public_shares + pl * i, pl);
+          cl2[k] = ct_len[i];
+          tm2[k] = times[i];
+        }
+        rc = janus_hpke_open_input_shares(fallback_opener, m, task_id, enc2.data(), ct2.data(),
+                                          cl2.data(), ct_stride, ids2.data(), tm2.data(),
+                                          pl ? pub2.data() : nullptr, d.public_share_len,
+                                          d.helper_share_len, require_taskprov, sh2.data(),
+                                          hs2.data());
+        if (rc) return rc == JANUS_HPKE_EDEVICE ? PRIO3_EDEVICE : PRIO3_EINVAL;
+        for (uint32_t k = 0; k < m; k++) {
+          const size_t i = idx[k];
+          memcpy(&shares[(size_t)d.helper_share_len * i], &sh2[(size_t)d.helper_share_len * k],
+                 d.helper_share_len);
+          hs[i] = hs2[k];
+        }
+      }
+    }
+    std::vector<uint8_t> late(n);
+    for (uint32_t i = 0; i < n; i++) {
+      late[i] = hs[i] == 0 && times[i] > report_deadline;
+      acc[i] = (!accept_mask || accept_mask[i]) && hs[i] == 0 && !late[i];
+    }
     rc = prio3_helper_prepare_aggregate_batch(e, n, report_ids, public_shares, shares.data(),
                                               leader_prep_shares, segment_ids, acc.data(),
                                               n_segments, prep_msgs_out, status_out,
                                               agg_shares_out, counts_out);
     if (rc) return rc;
     for (uint32_t i = 0; i < n; i++)
-      if (hs[i]) status_out[i] = (uint8_t)(0x80u | hs[i]);
+      if (hs[i])
+        status_out[i] = (uint8_t)(0x80u | hs[i]);
+      else if (late[i])
+        status_out[i] = (uint8_t)PRIO3_STATUS_REPORT_TOO_EARLY;
     return PRIO3_OK;
   }
   ExecJob job;
@@ -5016,10 +5123,40 @@ int prio3_helper_aggregate_init_batch(
   job.ct_len = ct_len;
   job.ct_stride = ct_stride;
   job.require_taskprov = require_taskprov ? 1 : 0;
+  job.fallback = fallback_opener;
+  job.deadline = report_deadline;
   const int rc = exec_submit(&job);
   if (rc) return rc;
   run_release(job.run, nullptr, false);
   return PRIO3_OK;
+}
+
+// the plain form: no fallback keypair, no report deadline, public shares of 0 or 32 bytes
+int prio3_helper_aggregate_init_batch(
+    prio3_engine* e, janus_hpke_opener* opener, uint32_t n, const uint8_t task_id[32],
+    int require_taskprov, const uint8_t* report_ids, const uint64_t* times,
+    const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct, const uint32_t* ct_len,
+    uint32_t ct_stride, const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
+    const uint8_t* accept_mask, uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out,
+    uint8_t* agg_shares_out, uint64_t* counts_out) {
+  return helper_aggregate_init(e, opener, nullptr, UINT64_MAX, 32, n, task_id, require_taskprov,
+                               report_ids, times, public_shares, enc, ct, ct_len, ct_stride,
+                               leader_prep_shares, segment_ids, accept_mask, n_segments,
+                               prep_msgs_out, status_out, agg_shares_out, counts_out);
+}
+
+int prio3_helper_aggregate_init_batch_ex(
+    prio3_engine* e, janus_hpke_opener* opener, janus_hpke_opener* fallback_opener,
+    uint64_t report_deadline, uint32_t n, const uint8_t task_id[32], int require_taskprov,
+    const uint8_t* report_ids, const uint64_t* times, const uint8_t* public_shares,
+    const uint8_t* enc, const uint8_t* ct, const uint32_t* ct_len, uint32_t ct_stride,
+    const uint8_t* leader_prep_shares, const uint32_t* segment_ids, const uint8_t* accept_mask,
+    uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out, uint8_t* agg_shares_out,
+    uint64_t* counts_out) {
+  return helper_aggregate_init(e, opener, fallback_opener, report_deadline, 64, n, task_id,
+                               require_taskprov, report_ids, times, public_shares, enc, ct,
+                               ct_len, ct_stride, leader_prep_shares, segment_ids, accept_mask,
+                               n_segments, prep_msgs_out, status_out, agg_shares_out, counts_out);
 }
 
 int prio3_accumulate(prio3_batch* b, const uint32_t* segment_ids, const uint8_t* accept_mask,

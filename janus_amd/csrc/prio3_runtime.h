@@ -138,12 +138,18 @@ struct ExecJob {
   const uint32_t* ct_len = nullptr;             // [n]
   uint32_t ct_stride = 0;
   int require_taskprov = 0;
+  // prio3_helper_aggregate_init_batch_ex: a report whose open under `opener` ends in
+  // HpkeDecryptError is opened again under `fallback` (the global keypair of the same config id,
+  // aggregator.rs:1864-1878) in the same launch; a report with times[i] > deadline gets
+  // 0x80 | ReportTooEarly (aggregator.rs:2004-2015) unless the open rejected it
+  janus_hpke_opener* fallback = nullptr;
+  uint64_t deadline = UINT64_MAX;  // seconds; UINT64_MAX: no check
   // results
   int rc = 0;
   Run* run = nullptr;  // holds one reference for this job
   uint32_t c0 = 0;     // the job's first column in the run
   uint32_t slot = 0;   // the job's verify-key slot in its group
-  uint32_t tslot = 0;  // the job's task slot in its group (sealed-input jobs)
+  uint32_t tslot = 0;  // the job's (task, deadline) slot in its group (sealed-input jobs)
   uint32_t seg0 = 0;   // the job's first segment among the group's
   uint32_t pad0 = 0;   // pad columns [pad0, c0) before the job (aligned aggregating jobs)
 };
@@ -176,7 +182,9 @@ uint64_t exec_load(int exec_id);
 // and receive [max_seg][agg_len] aggregate shares + [max_seg] u64 counts.
 // Groups of sealed-input jobs (ExecJob::opener) stage no helper shares (len[2] = 0) but, per
 // report, the HPKE ciphertext: enc [cap][nenc], ct [cap][ct_stride], ct_len (u32), the report time
-// (u64) and the task slot (u16), plus the task-ID table [HPKE_MAX_TASKS][8] (BE words).
+// (u64) and the task slot (u16), plus the task-ID table [HPKE_MAX_TASKS][8] (BE words) and the
+// report-deadline table [HPKE_MAX_TASKS] (u64 seconds), both indexed by the task slot: a slot
+// stands for one (task ID, deadline) pair, so two jobs of a task with different deadlines coalesce.
 struct IoLayout {
   size_t len[4], off[4];
   size_t slot_off, tab_off, msg_off, status_off, msg_len;
@@ -184,6 +192,7 @@ struct IoLayout {
   uint32_t max_seg;
   uint32_t nenc = 0, ct_stride = 0;  // ct_stride > 0: a sealed-input group
   size_t enc_off = 0, ct_off = 0, ctlen_off = 0, time_off = 0, tslot_off = 0, ttab_off = 0;
+  size_t dtab_off = 0;
   size_t bytes;
 };
 // job: the group's first job (its opener and ciphertext stride shape a sealed-input group)
@@ -201,6 +210,8 @@ struct GroupView {
   const IoLayout* L = nullptr;  // the staging layout (engine_io_layout of the group's first job)
   janus_hpke_opener* opener = nullptr;  // sealed-input group: the keypair its reports open with
   int require_taskprov = 0;
+  janus_hpke_opener* fallback = nullptr;  // the keypair its HpkeDecryptError reports are retried with
+  bool deadlines = false;  // some job of the group carries a report deadline
 };
 // segments one group can aggregate (its aggregating jobs' n_segments summed)
 constexpr uint32_t EXEC_MAX_SEGS = 1024;
@@ -372,6 +383,7 @@ struct HpkeLayout {
 };
 constexpr uint32_t HPKE_MAX_TASKS = 256;
 size_t hpke_opener_nenc(const janus_hpke_opener* o);
+uint32_t hpke_opener_kem(const janus_hpke_opener* o);  // the KEM id (the layout of enc)
 uint64_t hpke_opener_key(const janus_hpke_opener* o);  // keypair + suite (+ timing option)
 // The open kernel over a sealed-input prepare group, on the group's stream: inputs from the mapped
 // staging, the helper shares (zeroed unless opened) and the open status into the run.
@@ -384,6 +396,9 @@ struct HpkeGroupArgs {
   const uint16_t* task_slot;
   const uint32_t* task_tab;
   uint8_t *pt, *shares, *status;  // device: plaintext scratch [n][ct_stride], outputs
+  // retry pass: the launch opens reports idx[0 .. *n_idx) only (device memory; nullable: all n)
+  const uint32_t* idx = nullptr;
+  const uint32_t* n_idx = nullptr;
 };
 int hpke_open_group_launch(janus_hpke_opener* o, const HpkeGroupArgs& a, hipStream_t st);
 int hpke_opener_device(const janus_hpke_opener* o);

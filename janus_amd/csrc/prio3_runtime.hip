@@ -1001,8 +1001,11 @@ struct PrepPolicy {
     prio3_engine* lead = nullptr;
     std::vector<const prio3_engine*> keys;  // verify-key table, slot = index
     std::vector<std::array<uint8_t, 32>> tasks;  // sealed-input groups: task-ID table, slot = index
+    std::vector<uint64_t> deadlines;  // the slots' report deadlines (a slot = task ID + deadline)
     janus_hpke_opener* opener = nullptr;
+    janus_hpke_opener* fallback = nullptr;
     int require_taskprov = 0;
+    bool any_deadline = false;
     uint32_t n = 0, cap = 0, jobs = 0, nseg = 0, align = 1;
     IoLayout L;
     Run* run = nullptr;
@@ -1012,6 +1015,7 @@ struct PrepPolicy {
   static bool create(State& s, Job* j, size_t* bytes) {
     s.lead = j->e;
     s.opener = j->opener;
+    s.fallback = j->fallback;
     s.require_taskprov = j->require_taskprov;
     IoLayout l1, l2;
     engine_io_layout(j->e, 1, &l1, j);
@@ -1031,7 +1035,9 @@ struct PrepPolicy {
     if (k == s.keys.size() && s.keys.size() >= exec_max_keys()) return false;
     uint32_t t = 0;
     if (j->opener) {
-      while (t < s.tasks.size() && memcmp(s.tasks[t].data(), j->task_id, 32)) t++;
+      while (t < s.tasks.size() &&
+             (s.deadlines[t] != j->deadline || memcmp(s.tasks[t].data(), j->task_id, 32)))
+        t++;
       if (t == s.tasks.size() && s.tasks.size() >= HPKE_MAX_TASKS) return false;
     }
     const uint32_t al = j->nseg ? s.align : 1u;
@@ -1044,6 +1050,8 @@ struct PrepPolicy {
       std::array<uint8_t, 32> id;
       memcpy(id.data(), j->task_id, 32);
       s.tasks.push_back(id);
+      s.deadlines.push_back(j->deadline);
+      if (j->deadline != UINT64_MAX) s.any_deadline = true;
     }
     j->tslot = t;
     j->pad0 = s.n;
@@ -1090,6 +1098,7 @@ struct PrepPolicy {
         const uint8_t* b = j->task_id + 4 * i;
         tab[i] = (uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3];
       }
+      ((uint64_t*)(g.p + L.dtab_off))[j->tslot] = j->deadline;
     }
     // group segment ids: the job's own ids shifted to its segment range (an id >= its n_segments
     // stays out of every aggregate: 0xFFFFFFFF); a prepare-only job's reports are out
@@ -1131,6 +1140,8 @@ struct PrepPolicy {
     v.L = &s.L;
     v.opener = s.opener;
     v.require_taskprov = s.require_taskprov;
+    v.fallback = s.fallback;
+    v.deadlines = s.any_deadline;
     h->s = &s;
     return engine_group_issue(s.lead, v, &h->gr, own_queue);
   }

@@ -37,10 +37,12 @@ STATUS_PREP_MSG = 3
 STATUS_PREP_NEXT = 4
 STATUS_PEER_MISMATCH = 5
 STATUS_INPUT_SHARE_DECODE = 6
-#: merged statuses of prio3_helper_aggregate_init_batch: 0x80 | the DAP PrepareError of a report
-#: the input-share open rejected before its VDAF ran (aggregator.rs:1847-1983)
+#: merged statuses of prio3_helper_aggregate_init_batch[_ex]: 0x80 | the DAP PrepareError of a
+#: report the helper rejected before its VDAF ran (aggregator.rs:1847-2015): the input-share open
+#: and decode first, then the report deadline
 STATUS_HPKE_DECRYPT = 0x84
 STATUS_INVALID_MESSAGE = 0x88
+STATUS_REPORT_TOO_EARLY = 0x89
 
 #: prio ``PingPongError`` variant for each status (error.rs:365-428 maps these to labels).
 STATUS_PINGPONG_ERROR = {
@@ -104,6 +106,7 @@ EXPORTED_SYMBOLS = (
     "prio3_device_combine_metadata", "prio3_engine_create_ex", "prio3_engine_create_mask",
     "prio3_engine_create_devices", "prio3_engine_members", "prio3_executor_control",
     "prio3_executor_stats_get", "prio3_helper_aggregate_init_batch",
+    "prio3_helper_aggregate_init_batch_ex",
     "prio3_leader_prepare_next_aggregate_batch",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
@@ -157,6 +160,9 @@ def load_library() -> C.CDLL:
     u32 = C.c_uint32
     L.prio3_helper_aggregate_init_batch.argtypes = [vp, vp, u32, vp, C.c_int, vp, vp, vp, vp, vp,
                                                     vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.prio3_helper_aggregate_init_batch_ex.argtypes = [vp, vp, vp, C.c_uint64, u32, vp, C.c_int, vp,
+                                                       vp, vp, vp, vp, vp, u32, vp, vp, vp, u32,
+                                                       vp, vp, vp, vp]
     L.prio3_debug_output_shares.argtypes = [vp, vp]
     L.prio3_batch_free.argtypes = [vp]
     L.prio3_batch_free.restype = None
@@ -512,13 +518,20 @@ class HelperEngine:
 
     def aggregate_init_batch(self, opener, task_id: bytes, report_ids, times, public_shares,
                              enc, ct, ct_len, leader_prep_shares, segment_ids=None,
-                             accept_mask=None, n_segments: int = 1, require_taskprov=False):
+                             accept_mask=None, n_segments: int = 1, require_taskprov=False,
+                             fallback_opener=None, report_deadline=None):
         """The helper's whole loop body for one job from the sealed input shares
         (prio3_helper_aggregate_init_batch; aggregator.rs:1794-2096): HPKE open with ``opener``
         (janus_amd.hpke.HpkeOpener), decode, prepare and accumulate in one coalesced launch.
         enc [n, Nenc], ct [n, ct_stride] (stride a multiple of 16), ct_len [n].  Returns
-        (prep_msgs, status [merged: STATUS_* or STATUS_HPKE_DECRYPT / STATUS_INVALID_MESSAGE],
-        agg [S, agg_len], counts [S])."""
+        (prep_msgs, status [merged: STATUS_* or STATUS_HPKE_DECRYPT / STATUS_INVALID_MESSAGE /
+        STATUS_REPORT_TOO_EARLY], agg [S, agg_len], counts [S]).
+
+        With ``fallback_opener`` (the global keypair of the same config id and KEM) and / or
+        ``report_deadline`` (seconds; a report with a later time gets STATUS_REPORT_TOO_EARLY) the
+        call is prio3_helper_aggregate_init_batch_ex: the reports ``opener`` cannot decrypt are
+        opened again with the fallback inside the same launch.  With both left at None it is the
+        plain entry point."""
         sz = self.sz
         ids = np.ascontiguousarray(report_ids, np.uint8)
         n = ids.shape[0]
@@ -543,6 +556,17 @@ class HelperEngine:
         agg = np.zeros((n_segments, sz.agg_share_len), np.uint8)
         cnt = np.zeros(n_segments, np.uint64)
         tid = (C.c_uint8 * 32).from_buffer_copy(task_id)
+        if fallback_opener is not None or report_deadline is not None:
+            deadline = (1 << 64) - 1 if report_deadline is None else int(report_deadline)
+            rc = load_library().prio3_helper_aggregate_init_batch_ex(
+                self.handle, None if opener is None else opener.handle,
+                None if fallback_opener is None else fallback_opener.handle, deadline, n, tid,
+                int(bool(require_taskprov)), _np_ptr(ids), _np_ptr(t), _np_ptr(pub), _np_ptr(e),
+                _np_ptr(c), _np_ptr(cl), c.shape[1], _np_ptr(lps), _np_ptr(seg), _np_ptr(acc),
+                n_segments, _np_ptr(msgs), _np_ptr(status), _np_ptr(agg), _np_ptr(cnt))
+            if rc:
+                raise RuntimeError(f"prio3_helper_aggregate_init_batch_ex failed (rc={rc})")
+            return msgs[:, :sz.prep_msg_len], status, agg, cnt
         rc = load_library().prio3_helper_aggregate_init_batch(
             self.handle, opener.handle, n, tid, int(bool(require_taskprov)), _np_ptr(ids),
             _np_ptr(t), _np_ptr(pub), _np_ptr(e), _np_ptr(c), _np_ptr(cl), c.shape[1],
