@@ -1,6 +1,6 @@
 /*
- * janus_hpke.h -- C ABI of the batched HPKE opener for DAP input shares on MI355X (gfx950)
- * (SURVEY.md 8(f) row 2).
+ * janus_hpke.h -- C ABI of the batched HPKE opener for DAP input shares, and of the batched sealer
+ * (below: "Seal"), on MI355X (gfx950).
  *
  * It replaces, for a whole aggregation-job batch in one device call, the per-report decryption
  * in the helper's VdafOps::handle_aggregate_init_generic loop
@@ -57,6 +57,9 @@ enum {
   JANUS_HPKE_DECRYPT_ERROR = 4,    /* PrepareError::HpkeDecryptError */
   JANUS_HPKE_INVALID_MESSAGE = 8,  /* PrepareError::InvalidMessage (plaintext decode, extensions,
                                       input share length) */
+  /* Seal only; neither value is a DAP PrepareError code. */
+  JANUS_HPKE_SEAL_KEY_ERROR = 0x40,    /* the ephemeral key or pkR is not a valid key of the KEM */
+  JANUS_HPKE_SEAL_LENGTH_ERROR = 0x41, /* device form: a per-report length is past its row */
 };
 
 /* Whole-call return codes (same values as janus_prio3.h). */
@@ -118,6 +121,79 @@ int janus_hpke_open_device(janus_hpke_opener* opener, uint32_t n, const uint8_t*
 int janus_hpke_open(janus_hpke_opener* opener, uint32_t n, const uint8_t* enc, const uint8_t* ct,
                     const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* aad,
                     const uint32_t* aad_len, uint32_t aad_stride, uint8_t* pt, uint8_t* status);
+
+/* ---- Seal (RFC 9180 SetupBaseS + one Seal at sequence number 0) ---------------------------------
+ * The other direction of hpke.rs (hpke::seal, core/src/hpke.rs:167-189), which Janus calls in the
+ * client, in the helper's aggregate-share handler and in the leader's collection job driver.
+ * KEM DHKEM(X25519, HKDF-SHA256) or DHKEM(P-256, HKDF-SHA256) -- the two of Janus's own hpke
+ * layer; X448 / P-521 / P-384 are JANUS_HPKE_EUNSUPPORTED -- with every KDF and AEAD above.
+ *
+ * Randomness: the library generates none.  The caller supplies one ephemeral private key per
+ * report, d_sk_e[r][32] (Nsk = 32 for both KEMs), drawn from its CSPRNG, and must never reuse
+ * one: an X25519 key is any 32 bytes (clamped on the device), a P-256 key a big-endian scalar with
+ * 1 <= sk < n (0 and sk >= n give that report JANUS_HPKE_SEAL_KEY_ERROR, RFC 9180 7.1.2).
+ *
+ * Secret-indexed memory: the P-256 seal reads its per-sealer window tables (odd multiples of the
+ * base point and of pkR, in device memory) at addresses chosen by the digits of the ephemeral
+ * scalar.  The opener has no such access on a secret; the lookup is not hardened against an
+ * observer of the GPU's memory access pattern.
+ *
+ * Rows: d_enc[r][Nenc]; d_ct[r][ct_stride] holds ciphertext || 16-byte tag, d_ct_len[r] =
+ * plaintext length + 16, the rest of the row zero -- the layout
+ * janus_hpke_open_input_shares[_device] and prio3_helper_aggregate_init_batch[_ex] read.
+ * ct_stride is a multiple of 16 and >= plaintext length + 16, else JANUS_HPKE_EINVAL.  Status per
+ * report: JANUS_HPKE_OK or JANUS_HPKE_SEAL_KEY_ERROR (an invalid pkR -- an all-zero X25519 shared
+ * secret; a P-256 point with a wrong prefix, a non-canonical coordinate or off the curve --
+ * fails every report); a failed report's enc and ct rows are all zero and its ct_len is 0. */
+typedef struct janus_hpke_sealer janus_hpke_sealer;
+
+/* One sealer per (recipient public key pkR, application info), bound to one GPU.  A
+ * public_key_len that is not the KEM's Npk is JANUS_HPKE_EINVAL. */
+int janus_hpke_sealer_create(uint16_t kem_id, uint16_t kdf_id, uint16_t aead_id,
+                             const uint8_t* public_key, size_t public_key_len,
+                             const uint8_t* info, size_t info_len, int device,
+                             janus_hpke_sealer** out);
+void janus_hpke_sealer_destroy(janus_hpke_sealer* sealer);
+
+/* Generic seal with explicit plaintext d_pt[r][pt_stride] (d_pt_len[r] bytes) and AAD
+ * d_aad[r][aad_stride] (d_aad_len[r] bytes); pt_stride and aad_stride are multiples of 16 (0: no
+ * plaintext / no AAD).  The lengths live on the device, so a report whose d_pt_len exceeds
+ * pt_stride or ct_stride - 16, or whose d_aad_len exceeds aad_stride, gets
+ * JANUS_HPKE_SEAL_LENGTH_ERROR (rows zero, like a key error); the host form checks them first and
+ * returns JANUS_HPKE_EINVAL.  The host forms are plain blocking calls on a stream of the
+ * sealer's: no executor, no coalescing. */
+int janus_hpke_seal_device(janus_hpke_sealer* sealer, uint32_t n, const uint8_t* d_sk_e,
+                           const uint8_t* d_pt, const uint32_t* d_pt_len, uint32_t pt_stride,
+                           const uint8_t* d_aad, const uint32_t* d_aad_len, uint32_t aad_stride,
+                           uint8_t* d_enc, uint8_t* d_ct, uint32_t* d_ct_len, uint32_t ct_stride,
+                           uint8_t* d_status, void* stream);
+int janus_hpke_seal(janus_hpke_sealer* sealer, uint32_t n, const uint8_t* sk_e, const uint8_t* pt,
+                    const uint32_t* pt_len, uint32_t pt_stride, const uint8_t* aad,
+                    const uint32_t* aad_len, uint32_t aad_stride, uint8_t* enc, uint8_t* ct,
+                    uint32_t* ct_len, uint32_t ct_stride, uint8_t* status);
+
+/* DAP helper input shares of one task, what a client seals to the helper: the plaintext is
+ * PlaintextInputShare { extensions, payload = d_helper_shares[r][helper_share_len] }
+ * (messages/src/lib.rs:1326-1341) with no extension or, with_taskprov_extension, the one empty
+ * taskprov extension; the AAD is InputShareAad { task_id, metadata, public_share }
+ * (messages/src/lib.rs:1825-1872) from d_report_ids[r][16], d_times[r] and
+ * d_public_shares[r][public_share_len] (0, 32 or 64 bytes; else JANUS_HPKE_EINVAL).  Both are
+ * built on the device.  The plaintext length is 6 (10 with the extension) + helper_share_len. */
+int janus_hpke_seal_input_shares_device(janus_hpke_sealer* sealer, uint32_t n,
+                                        const uint8_t task_id[32], const uint8_t* d_sk_e,
+                                        const uint8_t* d_report_ids, const uint64_t* d_times,
+                                        const uint8_t* d_public_shares, uint32_t public_share_len,
+                                        const uint8_t* d_helper_shares, uint32_t helper_share_len,
+                                        int with_taskprov_extension, uint8_t* d_enc, uint8_t* d_ct,
+                                        uint32_t* d_ct_len, uint32_t ct_stride, uint8_t* d_status,
+                                        void* stream);
+int janus_hpke_seal_input_shares(janus_hpke_sealer* sealer, uint32_t n, const uint8_t task_id[32],
+                                 const uint8_t* sk_e, const uint8_t* report_ids,
+                                 const uint64_t* times, const uint8_t* public_shares,
+                                 uint32_t public_share_len, const uint8_t* helper_shares,
+                                 uint32_t helper_share_len, int with_taskprov_extension,
+                                 uint8_t* enc, uint8_t* ct, uint32_t* ct_len, uint32_t ct_stride,
+                                 uint8_t* status);
 
 /* The GPU's HPKE executor (shared by every opener on the GPU): counters, and control -- "hold"
  * 1/0 (tests queue jobs behind it; expires by itself after 30 s, or after N ms for hold = N > 1),

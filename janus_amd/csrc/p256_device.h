@@ -336,4 +336,131 @@ DEV bool ecdh(const int8_t* dig, const uint8_t* enc, uint32_t dh_be[8]) {
   return ok;
 }
 
+// -------------------------------------------------------------------------------------
+// The seal side (hpke.hip k_hpke_seal): the scalar is the report's ephemeral key, different in
+// every lane, and the two points -- the base point G and the recipient's pkR -- are fixed per
+// sealer.  Their odd multiples T, 3T, .., 15T (affine, canonical) are built once per sealer
+// (odd_multiples, one work-item per point) and stay in device memory; the window loop reads them
+// at a per-lane index, i.e. at an address that depends on the digits of the secret scalar.
+// -------------------------------------------------------------------------------------
+constexpr uint32_t kOrder[8] = {0xfc632551u, 0xf3b9cac2u, 0xa7179e84u, 0xbce6faadu,  // n, LE limbs
+                                0xffffffffu, 0xffffffffu, 0x00000000u, 0xffffffffu};
+constexpr fp kGx = {{0xd898c296u, 0xf4a13945u, 0x2deb33a0u, 0x77037d81u, 0x63a440f2u, 0xf8bce6e5u,
+                     0xe12c4247u, 0x6b17d1f2u}};
+constexpr fp kGy = {{0x37bf51f5u, 0xcbb64068u, 0x6b315eceu, 0x2bce3357u, 0x7c0f9e16u, 0x8ee7eb4au,
+                     0xfe1a7f9bu, 0x4fe342e2u}};
+constexpr int kTabWords = 8 * 2 * 8;  // one point's table: (2i+1)T as x || y, i = 0..7
+
+// an uncompressed SEC1 point 0x04 || X || Y, validated as ecdh validates enc
+DEV bool decode_point(const uint8_t* enc, fp& x, fp& y) {
+  constexpr fp B = {{0x27d2604bu, 0x3bce3c3eu, 0xcc53b0f6u, 0x651d06b0u, 0x769886bcu, 0xb3ebbd55u,
+                     0xaa3a93e7u, 0x5ac635d8u}};
+  bool ok = enc[0] == 0x04;
+  ok = from_be(enc + 1, x) && ok;
+  ok = from_be(enc + 33, y) && ok;
+  const fp rhs = add(sub(mul(sqr(x), x), mul_small(x, 3)), B);
+  return ok && eq(sqr(y), rhs);
+}
+
+DEV void to_affine(const jac& P, fp& x, fp& y) {
+  const fp zi = inv(P.Z), zi2 = sqr(zi);
+  x = freeze(mul(P.X, zi2));
+  y = freeze(mul(P.Y, mul(zi2, zi)));
+}
+
+// tab[2i], tab[2i+1] = affine (2i+1)T for a point T of order n: (2i+1)T = (2i-1)T + 2T, and
+// (2i-1)T != +-2T for i <= 7.  Once per sealer, so each entry takes its own inversion.
+DEV void odd_multiples(const fp& x, const fp& y, fp* tab) {
+  constexpr fp ONE = {{1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
+  tab[0] = x;
+  tab[1] = y;
+  fp x2, y2;
+  to_affine(dbl(jac{x, y, ONE}), x2, y2);
+  jac T{x, y, ONE};
+#pragma unroll 1
+  for (int i = 1; i < 8; i++) {
+    T = madd(T, x2, y2);
+    fp ax, ay;
+    to_affine(T, ax, ay);
+    tab[2 * i] = ax;
+    tab[2 * i + 1] = ay;
+  }
+}
+
+// The ephemeral private key (LE limbs s) -> the odd scalar k' the window loop takes: k' = s for an
+// odd s, else n - s, which negates the point (negated: the caller negates y back).  False for s = 0
+// and s >= n (RFC 9180 7.1.2).
+DEV bool seal_scalar(const uint32_t s[8], uint32_t k[8], bool& negated) {
+  uint32_t d[8], nz = 0, dnz = 0;
+  int64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int64_t t = (int64_t)kOrder[i] - s[i] + br;
+    d[i] = (uint32_t)t;
+    br = t >> 32;  // 0 or -1
+    nz |= s[i];
+    dnz |= d[i];
+  }
+  negated = !(s[0] & 1u);
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = negated ? d[i] : s[i];
+  return nz != 0 && br == 0 && dnz != 0;
+}
+
+// k' T for an odd k' in [1, n - 2] over T's table (tab: kTabWords words, 16-byte aligned).  The
+// digits of the regular signed window recoding (hpke.hip p256_recode) have a closed form for an
+// odd k': the running value after i steps is (k' >> 4i) | 1, so d_i = (((k' >> 4i) & 31) | 1) - 16
+// and the top digit is (k' >> 252) | 1.  They are taken most significant first by shifting k'
+// four bits a step -- no digit array, whose per-lane index would put it in scratch.  The
+// doubling case of the last window is ecdh's (the D / S select), per lane here.
+DEV jac mul_window(const uint32_t kp[8], const uint4* __restrict__ tab) {
+  constexpr fp ONE = {{1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
+  uint32_t k[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = kp[i];
+  auto load = [&](uint32_t a, fp& tx, fp& ty) {  // (2a+1)T
+    const uint4 x0 = tab[4 * a], x1 = tab[4 * a + 1], y0 = tab[4 * a + 2], y1 = tab[4 * a + 3];
+    tx = fp{{x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w}};
+    ty = fp{{y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w}};
+  };
+  // the next digit's five bits: the low bit of the nibble on top, then the nibble below it
+  auto next = [&](fp& tx, fp& ty) {
+    const uint32_t low = (k[7] >> 28) & 1u;
+#pragma unroll
+    for (int i = 7; i > 0; i--) k[i] = __builtin_amdgcn_alignbit(k[i], k[i - 1], 28);
+    k[0] <<= 4;
+    const int d = (int)((low << 4) | (k[7] >> 28) | 1u) - 16;
+    load((uint32_t)(d < 0 ? -d : d) >> 1, tx, ty);
+    const fp ny = neg(ty);
+#pragma unroll
+    for (int i = 0; i < 8; i++) ty.v[i] = d < 0 ? ny.v[i] : ty.v[i];
+  };
+  jac R;
+  load(k[7] >> 29, R.X, R.Y);  // top digit (k' >> 252) | 1
+  R.Z = ONE;
+#pragma unroll 1
+  for (int i = kDigits - 2; i >= 1; i--) {
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) R = dbl(R);
+    fp tx, ty;
+    next(tx, ty);
+    R = madd(R, tx, ty);
+  }
+#pragma unroll 1
+  for (int j = 0; j < 4; j++) R = dbl(R);
+  fp tx, ty;
+  next(tx, ty);
+  const jac D = dbl(R);
+  const jac S = madd(R, tx, ty);
+  const bool dbl_case = is_zero(S.Z);
+  jac O;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    O.X.v[i] = dbl_case ? D.X.v[i] : S.X.v[i];
+    O.Y.v[i] = dbl_case ? D.Y.v[i] : S.Y.v[i];
+    O.Z.v[i] = dbl_case ? D.Z.v[i] : S.Z.v[i];
+  }
+  return O;
+}
+
 }  // namespace p256

@@ -64,8 +64,9 @@ constexpr uint64_t IV384[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull, 0x9
 
 // st <- compress(st, w): w[16] the block's big-endian 64-bit words (consumed as schedule space).
 // Out of line on the device: one copy per kernel (a compression is ~3.5 k instructions and the
-// key schedules call it a dozen times; inlined, hpke.hip took minutes to compile).
-__host__ __device__ __noinline__ void compress(uint64_t st[8], uint64_t w[16]) {
+// key schedules call it a dozen times; inlined, hpke.hip took minutes to compile).  `inline` for
+// the host definition only: hpke.hip and hpke_seal.hip both include this header.
+inline __host__ __device__ __noinline__ void compress(uint64_t st[8], uint64_t w[16]) {
   constexpr uint64_t K[80] = {
       0x428a2f98d728ae22ull, 0x7137449123ef65cdull, 0xb5c0fbcfec4d3b2full, 0xe9b5dba58189dbbcull,
       0x3956c25bf348b538ull, 0x59f111f1b605d019ull, 0x923f82a4af194f9bull, 0xab1c5ed5da6d8118ull,

@@ -116,6 +116,8 @@ HPKE_EXPORTED_SYMBOLS = (
     "janus_hpke_open_device", "janus_hpke_open", "janus_hpke_set_timing", "janus_hpke_timing",
     "janus_hpke_selftest_p256", "janus_hpke_selftest_field", "janus_hpke_executor_stats_get",
     "janus_hpke_executor_control",
+    "janus_hpke_sealer_create", "janus_hpke_sealer_destroy", "janus_hpke_seal_device",
+    "janus_hpke_seal", "janus_hpke_seal_input_shares_device", "janus_hpke_seal_input_shares",
 )
 
 _lib = None
@@ -746,6 +748,40 @@ class HelperEngine:
             raise RuntimeError(f"prio3_client_generate_device failed (rc={rc})")
         if not sz.public_share_len:
             out["public_shares"] = out["public_shares"][:, :0]
+        return out
+
+    def generate_sealed_reports_device(self, sealer, task_id: bytes, n: int, times, sk_e,
+                                       seed: int = 1, first_index: int = 0,
+                                       with_taskprov_extension: bool = False, stream=None) -> dict:
+        """``generate_reports_device`` followed, on the same stream, by
+        ``sealer.seal_input_shares_device`` (janus_amd.hpke.HpkeSealer on this engine's GPU): what
+        a helper actually receives.  The report IDs are the reports' nonces.  times [n] (8-byte
+        integers) and sk_e [n, 32] (uint8, one ephemeral private key per report from the caller's
+        CSPRNG) are torch tensors on the GPU.  Returns the client's dict plus enc [n, Nenc],
+        ct [n, stride], ct_len [n] (int32) and seal_status [n]."""
+        import torch
+        from .hpke import NSK_E, sealed_stride
+        if len(task_id) != 32:
+            raise ValueError("task_id must be 32 bytes")
+        if sealer.device != self.device:
+            raise ValueError("the sealer is bound to another GPU than the engine")
+        if tuple(times.shape) != (n,) or tuple(sk_e.shape) != (n, NSK_E):
+            raise ValueError(f"times must be [{n}] and sk_e [{n}, {NSK_E}]")
+        if self.sz.public_share_len not in (0, 32, 64):
+            raise ValueError("the sealer takes public shares of 0, 32 or 64 bytes")
+        out = self.generate_reports_device(n, seed=seed, first_index=first_index, stream=stream)
+        dev = torch.device("cuda", self.device)
+        out["enc"] = torch.empty((n, sealer.nenc), dtype=torch.uint8, device=dev)
+        out["ct"] = torch.empty((n, sealed_stride(self.sz.helper_share_len,
+                                                  with_taskprov_extension)),
+                                dtype=torch.uint8, device=dev)
+        out["ct_len"] = torch.empty(n, dtype=torch.int32, device=dev)
+        out["seal_status"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        sealer.seal_input_shares_device(
+            task_id, sk_e, out["nonces"], times,
+            out["public_shares"] if self.sz.public_share_len else None, out["helper_shares"],
+            out["enc"], out["ct"], out["ct_len"], out["seal_status"],
+            with_taskprov_extension=with_taskprov_extension, stream=stream)
         return out
 
     # ---- measurement ----------------------------------------------------------------
