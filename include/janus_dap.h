@@ -119,6 +119,114 @@ int64_t janus_dap_agg_job_resp_encode_host(uint32_t n, const uint8_t* report_ids
                                            const uint8_t* prio3_status, const uint8_t* prep_msgs,
                                            uint32_t prep_msg_len, uint8_t* out);
 
+/* ---- Leader side: the two opposite directions --------------------------------------------
+ * The leader encodes the AggregationJobInitializeReq from the SoA buffers its device calls hold
+ * (report metadata, public shares, the HPKE ciphertexts of the helper input shares as
+ * janus_hpke_seal_input_shares_device writes them, and the prepare shares of
+ * prio3_device_leader_prepare_init) and decodes the helper's AggregationJobResp into the prepare
+ * messages prio3_device_leader_prepare_next reads -- Janus's loops at
+ * aggregation_job_driver.rs:417-437 and :657-752.
+ *
+ * Request encode.  A report with leader_status[r] != 0 is left out (the driver `continue`s past
+ * a report whose leader_initialized failed, :430-437).  index[r] receives the report's position
+ * in the request or JANUS_DAP_INDEX_NONE (the driver's stepped_aggregations); the response decode
+ * reads it.  Every PingPongMessage is Initialize { prep_shares[r] }.  enc_len must fit a u16.
+ *
+ * Host form: returns the body's length, or JANUS_DAP_EARG (a null pointer, an unknown query type,
+ * a ct_len above ct_stride) or JANUS_DAP_ETOOLONG (the PrepareInit list does not fit its u32
+ * length prefix; nothing usable is written).  out must hold
+ * janus_dap_agg_init_req_max_len(...) bytes.
+ *
+ * Device form: agg_param and batch_id are host memory (agg_param_len <= JANUS_DAP_AGG_PARAM_MAX;
+ * Prio3's is empty), every d_ pointer is device memory.  d_ct / d_ct_len are the rows the
+ * device sealer writes; a report whose ct_len is above ct_stride is left out like a failed one
+ * and counted in d_err[0], and no byte past a row is read.  d_err[1] is 1 when the list does not
+ * fit a u32: *d_out_len and *d_n_included are then 0 and the body is not written.  d_scratch:
+ * 4 * n + 16 * (n / 256 + 2) bytes, 8-byte aligned.  Runs on `stream` of the GPU that owns d_out, without
+ * host synchronisation; the calling thread's current device is left as it was. */
+#define JANUS_DAP_INDEX_NONE 0xFFFFFFFFu
+#define JANUS_DAP_AGG_PARAM_MAX 256
+enum { JANUS_DAP_EARG = -1, JANUS_DAP_EDEVICE = -2, JANUS_DAP_ETOOLONG = -3 };
+
+size_t janus_dap_agg_init_req_max_len(uint32_t n, uint32_t agg_param_len, uint8_t query_type,
+                                      uint32_t public_share_len, uint32_t enc_len,
+                                      uint32_t ct_stride, uint32_t prep_share_len);
+int64_t janus_dap_agg_init_req_encode_host(uint32_t n, const uint8_t* agg_param,
+                                           uint32_t agg_param_len, uint8_t query_type,
+                                           const uint8_t* batch_id, const uint8_t* report_ids,
+                                           const uint64_t* times, const uint8_t* public_shares,
+                                           uint32_t public_share_len, const uint8_t* config_ids,
+                                           const uint8_t* enc, uint32_t enc_len, const uint8_t* ct,
+                                           const uint32_t* ct_len, uint32_t ct_stride,
+                                           const uint8_t* prep_shares, uint32_t prep_share_len,
+                                           const uint8_t* leader_status, uint8_t* out,
+                                           uint32_t* index, uint32_t* n_included);
+int janus_dap_agg_init_req_encode_device(uint32_t n, const uint8_t* agg_param,
+                                         uint32_t agg_param_len, uint8_t query_type,
+                                         const uint8_t* batch_id, const uint8_t* d_report_ids,
+                                         const uint64_t* d_times, const uint8_t* d_public_shares,
+                                         uint32_t public_share_len, const uint8_t* d_config_ids,
+                                         const uint8_t* d_enc, uint32_t enc_len,
+                                         const uint8_t* d_ct, const uint32_t* d_ct_len,
+                                         uint32_t ct_stride, const uint8_t* d_prep_shares,
+                                         uint32_t prep_share_len, const uint8_t* d_leader_status,
+                                         uint8_t* d_out, uint64_t* d_out_len, uint32_t* d_index,
+                                         uint32_t* d_n_included, uint32_t* d_err, void* d_scratch,
+                                         void* stream);
+
+/* Response decode, in the engine's row order through index[] (n rows, n_included of them in the
+ * request).  prep_msgs[n][prep_msg_len]: a row is all zero unless its report continued.
+ * prepare_error[n]: 0xFF = the helper continued and the row holds its prepare message; any other
+ * value is the DAP PrepareError the report fails with.  A row with index[r] ==
+ * JANUS_DAP_INDEX_NONE keeps 0xFF and a zero row (its failure is in the caller's leader status).
+ * Per PrepareResp (aggregation_job_driver.rs:673-752):
+ *   Continue { Finish { prep_msg } } of prep_msg_len bytes -> 0xFF and the row
+ *   Reject(e), e <= 9                                       -> e
+ *   Finished                                                -> 5 (VdafPrepError, :714-732)
+ *   Continue with Initialize / Continue, or a Finish of another length -> 5 (:677-710)
+ * The whole response is rejected when it does not decode (a Reject code above 9, lib.rs:2185-2196,
+ * included), when its record count is not n_included or when a record's report ID is not the
+ * expected one at that position (:657-671).
+ *
+ * Host form: returns 0 or one of the JANUS_DAP_RESP_E* codes.  It decodes the whole body first
+ * (ELISTLEN, ETRAILING, EMALFORMED, EREJECT_CODE), then compares the count (ECOUNT) and the IDs
+ * (EID).
+ *
+ * Device form: speculative, like the request unpack.  It decodes any mix of the three regular
+ * shapes (Continue-Finish of prep_msg_len bytes, Finished, Reject) with no host help; any other
+ * record stops it with JANUS_DAP_RESP_IRREGULAR in *d_flags (and JANUS_DAP_RESP_MALFORMED when
+ * the record cannot decode) and the caller uses the host form.  *d_flags (device u32, zeroed
+ * here) is the OR of the JANUS_DAP_RESP_* bits; when it is non-zero the outputs are incomplete.
+ * d_body must be readable up to a dword past body_len.  d_scratch: 8 * (n_included + 2) bytes,
+ * 4-byte aligned.  Stream and device as for the request encode (the GPU that owns d_flags). */
+enum {
+  JANUS_DAP_RESP_IRREGULAR = 1,   /* a record of another shape: use the host form */
+  JANUS_DAP_RESP_LISTLEN = 2,     /* the list length runs past the body */
+  JANUS_DAP_RESP_TRAILING = 4,    /* bytes after the list */
+  JANUS_DAP_RESP_MALFORMED = 8,   /* a record or its PingPongMessage does not decode */
+  JANUS_DAP_RESP_REJECT_CODE = 16, /* Reject with a code above 9 */
+  JANUS_DAP_RESP_COUNT = 32,      /* the record count is not n_included */
+  JANUS_DAP_RESP_ID = 64          /* a record's report ID is not the expected one */
+};
+enum {
+  JANUS_DAP_RESP_ELISTLEN = -3,
+  JANUS_DAP_RESP_ETRAILING = -4,
+  JANUS_DAP_RESP_EMALFORMED = -5,
+  JANUS_DAP_RESP_EREJECT_CODE = -6,
+  JANUS_DAP_RESP_ECOUNT = -7,
+  JANUS_DAP_RESP_EID = -8
+};
+int janus_dap_agg_job_resp_unpack_host(uint32_t n, const uint32_t* index,
+                                       const uint8_t* report_ids, uint32_t n_included,
+                                       const uint8_t* body, size_t body_len, uint32_t prep_msg_len,
+                                       uint8_t* prep_msgs, uint8_t* prepare_error);
+int janus_dap_agg_job_resp_unpack_device(uint32_t n, const uint32_t* d_index,
+                                         const uint8_t* d_report_ids, uint32_t n_included,
+                                         const uint8_t* d_body, size_t body_len,
+                                         uint32_t prep_msg_len, uint8_t* d_prep_msgs,
+                                         uint8_t* d_prepare_error, uint32_t* d_flags,
+                                         void* d_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// dap_codec.hip -- DAP-09 wire format <-> SoA marshaling for the helper's aggregation-job init
+// dap_codec.hip -- DAP-09 wire format <-> SoA marshaling for both roles' aggregation-job init
 // on MI355X (gfx950); SURVEY 8(f) row 3.  See include/janus_dap.h for the encodings.
 //
 //  k_unpack_check / k_unpack_gather
@@ -11,12 +11,22 @@
 //                 AggregationJobResp: per-block counts of the two PrepareResp sizes, an
 //                 exclusive scan of the block totals, then each lane writes its record at its
 //                 byte offset (block-local prefix via __syncthreads_count-style LDS scan).
+//  k_req_count / k_req_scan / k_req_write
+//                 leader: AggregationJobInitializeReq from the SoA buffers; records differ in
+//                 length (ct_len) and failed reports are left out, so a scan over byte lengths
+//                 gives each report its offset; one lane per aligned output dword.
+//  k_runp_index / k_runp_check / k_runp_gather
+//                 leader: AggregationJobResp into prepare messages and per-report errors; one
+//                 workgroup indexes the three regular record shapes speculatively, then the
+//                 parallel passes compare report IDs and gather the messages.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/janus_dap.h"
+#include "prio3_runtime.h"
 
 #define DEV __device__ __forceinline__
 
@@ -235,6 +245,392 @@ __global__ __launch_bounds__(256) void k_resp_write(uint32_t n, const uint8_t* i
   } else {
     out[o] = 2;  // PrepareStepResult::Reject
     out[o + 1] = pe[r] != 0xFF ? pe[r] : 5;  // PrepareError (VdafPrepError for prio3 failures)
+  }
+}
+
+// ---- leader side: AggregationJobInitializeReq encode --------------------------------------
+// record: id[16] time[8] psl[4] pub | cfg[1] enc_len[2] enc | ct_len[4] ct | ml[4] 0 ps[4] share
+// = 44 + public_share_len + enc_len + ct_len + prep_share_len bytes.  A report takes part when
+// its leader status is 0 and its ct_len fits the row.
+constexpr uint32_t REQ_FIXED = 44;
+constexpr uint32_t REQ_CHUNK = 256;   // records per block of the count / write kernels
+constexpr uint32_t REQ_HDR_MAX = 4 + 256 + 1 + 32 + 4;
+
+struct ReqHdr {  // the body's bytes before the first PrepareInit (list length filled on the device)
+  uint8_t b[REQ_HDR_MAX];
+  uint32_t len;
+};
+struct ReqArgs {
+  uint32_t n, psl, enc_len, ct_stride, ps_len;
+  const uint8_t *ids, *pub, *cfg, *enc, *ct, *ps, *status;
+  const uint64_t* times;
+  const uint32_t* ct_len;
+  uint64_t* blk_bytes;  // [nb] per-chunk byte totals, then their exclusive scan
+  uint32_t* blk_cnt;    // [nb] per-chunk record counts, then their exclusive scan
+  uint32_t* rel;        // [n] chunk-local inclusive scan of the record lengths
+  uint8_t* out;
+  uint64_t* out_len;
+  uint32_t *index, *n_included, *err;  // err[0]: reports left out for ct_len > ct_stride,
+                                       // err[1]: the list does not fit a u32 (nothing written)
+};
+
+DEV uint32_t req_len(const ReqArgs& a, uint32_t r, bool count_oversize) {
+  if (r >= a.n || a.status[r] != 0) return 0;
+  const uint32_t cl = a.ct_len[r];
+  if (cl > a.ct_stride) {
+    if (count_oversize) atomicAdd(&a.err[0], 1u);
+    return 0;
+  }
+  return REQ_FIXED + a.psl + a.enc_len + a.ps_len + cl;  // host checked: no u32 overflow
+}
+
+// k_req_count: the chunk-local inclusive scans of the record lengths and of the included
+// reports (Hillis-Steele in LDS): rel[r] = bytes of the chunk up to and including report r,
+// index[r] = its position among the chunk's included reports (the write kernel adds the chunk's
+// base), and the chunk totals for k_req_scan
+__global__ __launch_bounds__(256) void k_req_count(ReqArgs a) {
+  __shared__ uint64_t s[256];
+  __shared__ uint32_t c[256];
+  const uint32_t t = threadIdx.x, r = blockIdx.x * REQ_CHUNK + t;
+  const uint32_t len = req_len(a, r, true);
+  s[t] = len;
+  c[t] = len != 0;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {
+    const uint64_t ts = t >= d ? s[t - d] : 0ull;
+    const uint32_t tc = t >= d ? c[t - d] : 0u;
+    __syncthreads();
+    s[t] += ts;
+    c[t] += tc;
+    __syncthreads();
+  }
+  if (r < a.n) {
+    a.rel[r] = (uint32_t)s[t];  // meaningless when the chunk passes 2^32: nothing is written then
+    a.index[r] = len ? c[t] - 1 : 0xFFFFFFFFu;
+  }
+  if (t == 255) {
+    a.blk_bytes[blockIdx.x] = s[255];
+    a.blk_cnt[blockIdx.x] = c[255];
+  }
+}
+
+// exclusive scans of the per-chunk byte totals and counts (one block, sequential 1024-chunk
+// tiles, as k_resp_scan), then the header, the list length and the totals
+__global__ __launch_bounds__(1024) void k_req_scan(uint32_t nb, ReqArgs a, ReqHdr h) {
+  __shared__ uint64_t sb[1024];
+  __shared__ uint32_t sc[1024];
+  __shared__ uint64_t carry_b;
+  __shared__ uint32_t carry_c;
+  if (threadIdx.x == 0) {
+    carry_b = 0;
+    carry_c = 0;
+  }
+  __syncthreads();
+  for (uint32_t base = 0; base < nb; base += 1024) {
+    const uint32_t i = base + threadIdx.x;
+    const uint64_t vb = i < nb ? a.blk_bytes[i] : 0ull;
+    const uint32_t vc = i < nb ? a.blk_cnt[i] : 0u;
+    sb[threadIdx.x] = vb;
+    sc[threadIdx.x] = vc;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+      const uint64_t tb = threadIdx.x >= d ? sb[threadIdx.x - d] : 0ull;
+      const uint32_t tc = threadIdx.x >= d ? sc[threadIdx.x - d] : 0u;
+      __syncthreads();
+      sb[threadIdx.x] += tb;
+      sc[threadIdx.x] += tc;
+      __syncthreads();
+    }
+    if (i < nb) {
+      a.blk_bytes[i] = carry_b + sb[threadIdx.x] - vb;
+      a.blk_cnt[i] = carry_c + sc[threadIdx.x] - vc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 1023) {
+      carry_b += sb[1023];
+      carry_c += sc[1023];
+    }
+    __syncthreads();
+  }
+  const uint64_t list = carry_b;
+  const bool fits = list <= 0xFFFFFFFFull;
+  if (fits && threadIdx.x < h.len - 4) a.out[threadIdx.x] = h.b[threadIdx.x];
+  if (threadIdx.x == 0) {
+    a.err[1] = fits ? 0u : 1u;
+    *a.out_len = fits ? h.len + list : 0ull;
+    *a.n_included = fits ? carry_c : 0u;
+    if (fits) {
+      uint8_t* p = a.out + h.len - 4;
+      p[0] = (uint8_t)(list >> 24);
+      p[1] = (uint8_t)(list >> 16);
+      p[2] = (uint8_t)(list >> 8);
+      p[3] = (uint8_t)list;
+    }
+  }
+}
+
+// byte k (k < record length) of report r's PrepareInit; cl = its ct_len
+DEV uint32_t req_byte(const ReqArgs& a, uint32_t r, uint32_t cl, uint32_t k) {
+  if (k < 16) return a.ids[16 * (size_t)r + k];
+  if (k < 24) return (uint32_t)(a.times[r] >> (8 * (23 - k))) & 0xFFu;
+  if (k < 28) return (a.psl >> (8 * (27 - k))) & 0xFFu;
+  k -= 28;
+  if (k < a.psl) return a.pub[(size_t)a.psl * r + k];
+  k -= a.psl;
+  if (k == 0) return a.cfg[r];
+  if (k < 3) return (a.enc_len >> (8 * (2 - k))) & 0xFFu;
+  k -= 3;
+  if (k < a.enc_len) return a.enc[(size_t)a.enc_len * r + k];
+  k -= a.enc_len;
+  if (k < 4) return (cl >> (8 * (3 - k))) & 0xFFu;
+  k -= 4;
+  if (k < cl) return a.ct[(size_t)a.ct_stride * r + k];
+  k -= cl;
+  if (k < 4) return ((5 + a.ps_len) >> (8 * (3 - k))) & 0xFFu;
+  if (k == 4) return 0;  // PingPongMessage::Initialize
+  if (k < 9) return (a.ps_len >> (8 * (8 - k))) & 0xFFu;
+  return a.ps[(size_t)a.ps_len * r + (k - 9)];
+}
+
+// the four source bytes of record bytes [k, k + 4) when they lie inside one byte field whose
+// array (base, `total` bytes, dword-aligned) covers the two aligned dwords ld_le32 reads
+DEV bool req_field_dword(const uint8_t* base, uint64_t total, uint64_t row_off, uint32_t fs,
+                         uint32_t flen, uint32_t k, uint32_t* v) {
+  if (k < fs || k + 4 > fs + flen) return false;
+  const uint64_t off = row_off + (k - fs);
+  if (((uintptr_t)base & 3u) || (off & ~3ull) + ((off & 3u) ? 8 : 4) > total) return false;
+  *v = ld_le32(base, off);
+  return true;
+}
+
+// value of the aligned output dword holding record bytes [k, k + 4) of report r (k + 4 <= its
+// length): a dword read of the field row when the four bytes lie in one byte field, else bytewise
+DEV uint32_t req_dword(const ReqArgs& a, uint32_t r, uint32_t cl, uint32_t k) {
+  const uint32_t f_pub = 28, f_enc = f_pub + a.psl + 3, f_ct = f_enc + a.enc_len + 4,
+                 f_ps = f_ct + cl + 9;
+  uint32_t v;
+  if (req_field_dword(a.ps, (uint64_t)a.n * a.ps_len, (uint64_t)a.ps_len * r, f_ps, a.ps_len, k, &v) ||
+      req_field_dword(a.ct, (uint64_t)a.n * a.ct_stride, (uint64_t)a.ct_stride * r, f_ct, cl, k, &v) ||
+      req_field_dword(a.pub, (uint64_t)a.n * a.psl, (uint64_t)a.psl * r, f_pub, a.psl, k, &v) ||
+      req_field_dword(a.enc, (uint64_t)a.n * a.enc_len, (uint64_t)a.enc_len * r, f_enc, a.enc_len, k, &v))
+    return v;
+  return req_byte(a, r, cl, k) | req_byte(a, r, cl, k + 1) << 8 | req_byte(a, r, cl, k + 2) << 16 |
+         req_byte(a, r, cl, k + 3) << 24;
+}
+
+// k_req_write: a block writes the bytes of REQ_SUB consecutive reports (of one chunk), one lane
+// per aligned dword of the output: the lane finds its report by a binary search of the block's
+// offsets in LDS, so adjacent lanes write adjacent dwords across record boundaries and read
+// adjacent bytes of the field rows.  Dwords that straddle two records are assembled bytewise; the
+// block's first and last dword, which it may share with its neighbour (or with the header), are
+// stored bytewise.
+constexpr uint32_t REQ_SUB = 16;
+__global__ __launch_bounds__(256) void k_req_write(ReqArgs a, uint32_t hdr_len) {
+  __shared__ uint32_t s_off[REQ_SUB + 1];  // s_off[i + 1]: chunk bytes up to and including report i
+  if (a.err[1]) return;  // the list does not fit a u32
+  const uint32_t t = threadIdx.x, r0 = blockIdx.x * REQ_SUB, chunk = r0 / REQ_CHUNK;
+  if (t <= REQ_SUB) {
+    const uint32_t r = r0 + t;  // s_off[t] belongs to report r - 1
+    uint32_t v = 0;
+    if (r % REQ_CHUNK != 0 || t) v = a.rel[(r <= a.n ? r : a.n) - 1];
+    s_off[t] = v;
+    if (t && r <= a.n && a.index[r - 1] != 0xFFFFFFFFu) a.index[r - 1] += a.blk_cnt[chunk];
+  }
+  __syncthreads();
+  const uint32_t b0 = s_off[0], b1 = s_off[REQ_SUB];
+  if (b0 == b1) return;
+  uint8_t* base = a.out + hdr_len + a.blk_bytes[chunk];
+  const uint32_t fixed = REQ_FIXED + a.psl + a.enc_len + a.ps_len;
+  // the report (of the block) that holds chunk byte x (b0 <= x < b1)
+  auto find = [&](uint32_t x) {
+    uint32_t lo = 0, hi = REQ_SUB - 1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_off[mid + 1] > x) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  };
+  const uint32_t mis = (uint32_t)((uintptr_t)(base + b0) & 3u);
+  const uint32_t nd = (mis + (b1 - b0) + 3) >> 2;
+  for (uint32_t j = t; j < nd; j += 256) {
+    const int64_t x0 = (int64_t)b0 - mis + 4 * (int64_t)j;  // dword j = chunk bytes [x0, x0 + 4)
+    uint8_t* p = base + x0;
+    const bool whole = x0 >= (int64_t)b0 && x0 + 4 <= (int64_t)b1;
+    if (whole) {
+      const uint32_t i = find((uint32_t)x0);
+      const uint32_t start = s_off[i], L = s_off[i + 1] - start, k = (uint32_t)x0 - start;
+      if (k + 4 <= L) {
+        *(uint32_t*)p = req_dword(a, r0 + i, L - fixed, k);
+        continue;
+      }
+    }
+    uint32_t v = 0;
+    for (int b = 0; b < 4; b++) {
+      const int64_t x = x0 + b;
+      if (x < (int64_t)b0 || x >= (int64_t)b1) continue;
+      const uint32_t i = find((uint32_t)x);
+      const uint32_t start = s_off[i];
+      const uint32_t byte = req_byte(a, r0 + i, s_off[i + 1] - start - fixed, (uint32_t)x - start);
+      if (whole) v |= byte << (8 * b); else p[b] = (uint8_t)byte;
+    }
+    if (whole) *(uint32_t*)p = v;
+  }
+}
+
+// ---- leader side: AggregationJobResp decode -----------------------------------------------
+// The three regular PrepareResp shapes: Continue { Finish { prep_msg[pml] } } = 26 + pml bytes,
+// Finished = 17, Reject(e) = 18.  Record offsets depend on every earlier record, so one workgroup
+// indexes the list first (k_runp_index) and the parallel passes read the index.
+enum : uint32_t { RK_CONT = 0, RK_FINISHED = 1, RK_REJECT = 2 };
+constexpr uint32_t RUNP_WIDTH = 1024;  // records speculated full-length per step
+// classes a lane reports for the record at its speculated offset (low byte of the LDS key)
+enum : uint32_t { RC_FINISHED = 1, RC_REJECT = 2, RC_BADCODE = 3, RC_IRREGULAR = 4,
+                  RC_MALFORMED = 5, RC_END = 6 };
+
+struct RunpArgs {
+  const uint8_t* body;  // readable up to a dword past body_len
+  uint64_t body_len;
+  uint32_t n, n_included, pml;
+  const uint32_t* index;
+  const uint8_t* ids;
+  uint8_t *msgs, *perr;
+  uint32_t* flags;
+  uint32_t* walked;  // scratch: records indexed
+  uint32_t* off;     // scratch [n_included]: record offsets from the body's start
+  uint8_t* kind;     // scratch [n_included]
+};
+
+// class of the record at byte o of a list ending at `end` (0: regular Continue-Finish)
+DEV uint32_t runp_classify(const uint8_t* b, uint64_t o, uint64_t end, uint32_t pml) {
+  if (o >= end) return RC_END;
+  if (o + 17 > end) return RC_MALFORMED;
+  const uint32_t ty = ld_u8(b, o + 16);
+  if (ty == 1) return RC_FINISHED;
+  if (ty == 2) {
+    if (o + 18 > end) return RC_MALFORMED;
+    return ld_u8(b, o + 17) <= 9 ? RC_REJECT : RC_BADCODE;
+  }
+  if (ty != 0 || o + 21 > end) return RC_MALFORMED;
+  const uint64_t ml = ld_be32(b, o + 17);
+  if (ml < 5 || o + 21 + ml > end) return RC_MALFORMED;
+  const uint32_t pty = ld_u8(b, o + 21);
+  const uint64_t x = ld_be32(b, o + 22);
+  if (pty == 2 && ml == 5 + x && x == pml) return 0;
+  if (pty == 0 || pty == 2) return ml == 5 + x ? RC_IRREGULAR : RC_MALFORMED;
+  if (pty != 1 || 9 + x > ml) return RC_MALFORMED;
+  return ml == 9 + x + ld_be32(b, o + 26 + x) ? RC_IRREGULAR : RC_MALFORMED;
+}
+
+// k_runp_index: one workgroup walks the list.  Per step lane i classifies the record that
+// starts at o + i * (26 + pml) -- where record r + i starts if the records before it are all
+// full-length; the first lane that does not see a regular Continue-Finish wins an LDS atomicMin
+// of (i << 8 | class); lanes before it write offset and kind, the walk steps over the short
+// record (Finished / Reject) and speculates again.  n / width + (short records) steps.
+__global__ __launch_bounds__(1024) void k_runp_index(RunpArgs a) {
+  __shared__ uint32_t first[3];
+  const uint32_t F = 26 + a.pml, t = threadIdx.x;
+  uint32_t fl = 0;
+  uint64_t end = a.body_len;
+  if (a.body_len < 4) {
+    fl = JANUS_DAP_RESP_LISTLEN;
+  } else {
+    const uint64_t list = ld_be32(a.body, 0);
+    if (4 + list > a.body_len) fl = JANUS_DAP_RESP_LISTLEN;
+    if (4 + list < a.body_len) fl = JANUS_DAP_RESP_TRAILING;
+    end = 4 + list;
+  }
+  uint32_t r = 0, slot = 0;
+  uint64_t o = 4;
+  if (t == 0) first[0] = 0xFFFFFFFFu;
+  __syncthreads();
+  while (!fl) {
+    const uint64_t mine = o + (uint64_t)t * F;
+    // a record past the expected count is the walk's end as well
+    const uint32_t c = r + t >= a.n_included ? RC_END : runp_classify(a.body, mine, end, a.pml);
+    if (c) atomicMin(&first[slot], t << 8 | c);
+    // three slots, one barrier per step: the slot of the next step was last read two steps ago
+    const uint32_t next = slot == 2 ? 0 : slot + 1;
+    if (t == 0) first[next] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint32_t f = first[slot];
+    slot = next;
+    const uint32_t k = f == 0xFFFFFFFFu ? RUNP_WIDTH : f >> 8, cls = f & 0xFFu;
+    if (t < k) {
+      a.off[r + t] = (uint32_t)mine;
+      a.kind[r + t] = RK_CONT;
+    }
+    r += k;
+    o += (uint64_t)k * F;
+    if (k == RUNP_WIDTH) continue;
+    if (cls == RC_FINISHED || cls == RC_REJECT) {
+      if (t == 0) {
+        a.off[r] = (uint32_t)o;
+        a.kind[r] = cls == RC_FINISHED ? RK_FINISHED : RK_REJECT;
+      }
+      r += 1;
+      o += cls == RC_FINISHED ? 17 : 18;
+      continue;
+    }
+    if (cls == RC_BADCODE) fl = JANUS_DAP_RESP_REJECT_CODE;
+    if (cls == RC_IRREGULAR) fl = JANUS_DAP_RESP_IRREGULAR;
+    if (cls == RC_MALFORMED) fl = JANUS_DAP_RESP_IRREGULAR | JANUS_DAP_RESP_MALFORMED;
+    if (cls == RC_END && (r != a.n_included || o != end)) fl = JANUS_DAP_RESP_COUNT;
+    break;
+  }
+  if (t == 0) {
+    *a.walked = r;
+    if (fl) atomicOr(a.flags, fl);
+  }
+}
+
+// k_runp_check: one lane per engine row: the record's report ID against the row's, and the
+// row's PrepareError (0xFF: the helper continued)
+__global__ __launch_bounds__(256) void k_runp_check(RunpArgs a) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n) return;
+  uint8_t pe = 0xFF;
+  const uint32_t j = a.index[r];
+  if (j != 0xFFFFFFFFu) {
+    if (j >= a.n_included) {
+      atomicOr(a.flags, (uint32_t)JANUS_DAP_RESP_COUNT);
+    } else if (j < *a.walked) {
+      const uint64_t o = a.off[j];
+      bool same = true;
+      for (uint32_t w = 0; w < 4; w++)
+        same = same && ld_le32(a.body, o + 4 * w) == ld_le32(a.ids, 16 * (uint64_t)r + 4 * w);
+      if (!same) atomicOr(a.flags, (uint32_t)JANUS_DAP_RESP_ID);
+      const uint32_t kd = a.kind[j];
+      if (kd == RK_FINISHED) pe = 5;  // VdafPrepError: the leader cannot be finished yet
+      if (kd == RK_REJECT) pe = (uint8_t)ld_u8(a.body, o + 17);
+    }
+  }
+  a.perr[r] = pe;
+}
+
+// k_runp_gather: one lane per dword of d_prep_msgs (rows of reports that did not continue are
+// zeroed); consecutive Continue records are consecutive in the body, so both sides coalesce
+__global__ __launch_bounds__(256) void k_runp_gather(RunpArgs a) {
+  const uint64_t total = (uint64_t)a.n * a.pml;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (4 * i >= total) return;
+  const uint32_t walked = *a.walked;
+  if ((a.pml & 3u) == 0) {
+    const uint32_t wpr = a.pml >> 2;
+    const uint32_t r = (uint32_t)(i / wpr), b = 4 * (uint32_t)(i - (uint64_t)r * wpr);
+    const uint32_t j = a.index[r];
+    uint32_t v = 0;
+    if (j < a.n_included && j < walked && a.kind[j] == RK_CONT)
+      v = ld_le32(a.body, (uint64_t)a.off[j] + 26 + b);
+    ((uint32_t*)a.msgs)[i] = v;
+    return;
+  }
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint64_t q = 4 * i + k;
+    if (q >= total) break;
+    const uint32_t r = (uint32_t)(q / a.pml), c = (uint32_t)(q - (uint64_t)r * a.pml);
+    const uint32_t j = a.index[r];
+    a.msgs[q] = (j < a.n_included && j < walked && a.kind[j] == RK_CONT)
+                    ? a.body[(uint64_t)a.off[j] + 26 + c] : 0;
   }
 }
 
@@ -561,6 +957,289 @@ int64_t janus_dap_agg_job_resp_encode_host(uint32_t n, const uint8_t* ids, const
   out[2] = (uint8_t)(body >> 8);
   out[3] = (uint8_t)body;
   return (int64_t)o;
+}
+
+// ---- leader side --------------------------------------------------------------------------
+namespace {
+void put_be32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)(v >> 24);
+  p[1] = (uint8_t)(v >> 16);
+  p[2] = (uint8_t)(v >> 8);
+  p[3] = (uint8_t)v;
+}
+size_t req_hdr_len(uint32_t apl, uint8_t qt) {
+  return 4 + (size_t)apl + 1 + (qt == JANUS_DAP_QUERY_FIXED_SIZE ? 32 : 0) + 4;
+}
+// the body up to the list length (which the caller fills at the returned offset)
+size_t req_hdr_put(uint8_t* out, const uint8_t* ap, uint32_t apl, uint8_t qt, const uint8_t* bid) {
+  size_t o = 0;
+  put_be32(out, apl);
+  o += 4;
+  if (apl) memcpy(out + o, ap, apl);
+  o += apl;
+  out[o++] = qt;
+  if (qt == JANUS_DAP_QUERY_FIXED_SIZE) {
+    memcpy(out + o, bid, 32);
+    o += 32;
+  }
+  return o;
+}
+bool req_args_ok(uint32_t n, const uint8_t* ap, uint32_t apl, uint8_t qt, const uint8_t* bid,
+                 uint32_t psl, uint32_t enc_len, uint32_t ct_stride, uint32_t ps_len) {
+  if (qt != JANUS_DAP_QUERY_TIME_INTERVAL && qt != JANUS_DAP_QUERY_FIXED_SIZE) return false;
+  if ((apl && !ap) || (qt == JANUS_DAP_QUERY_FIXED_SIZE && !bid)) return false;
+  if (enc_len > 0xFFFF) return false;
+  // one record stays far below 2^32 bytes (the kernels index a record's bytes in 32 bits)
+  return (uint64_t)REQ_FIXED + psl + enc_len + ct_stride + ps_len < (1ull << 31);
+}
+int device_of(const void* p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return at.device;
+}
+}  // namespace
+
+size_t janus_dap_agg_init_req_max_len(uint32_t n, uint32_t apl, uint8_t qt, uint32_t psl,
+                                      uint32_t enc_len, uint32_t ct_stride, uint32_t ps_len) {
+  return req_hdr_len(apl, qt) +
+         (size_t)n * ((size_t)REQ_FIXED + psl + enc_len + ct_stride + ps_len) + 8;
+}
+
+int64_t janus_dap_agg_init_req_encode_host(uint32_t n, const uint8_t* ap, uint32_t apl, uint8_t qt,
+                                           const uint8_t* bid, const uint8_t* ids,
+                                           const uint64_t* times, const uint8_t* pub, uint32_t psl,
+                                           const uint8_t* cfg, const uint8_t* enc,
+                                           uint32_t enc_len, const uint8_t* ct,
+                                           const uint32_t* ct_len, uint32_t ct_stride,
+                                           const uint8_t* ps, uint32_t ps_len,
+                                           const uint8_t* status, uint8_t* out, uint32_t* index,
+                                           uint32_t* n_included) {
+  if (!out || !index || !n_included || !req_args_ok(n, ap, apl, qt, bid, psl, enc_len, ct_stride,
+                                                    ps_len))
+    return JANUS_DAP_EARG;
+  if (n && (!ids || !times || !cfg || !ct_len || !status || (psl && !pub) || (enc_len && !enc) ||
+            (ct_stride && !ct) || (ps_len && !ps)))
+    return JANUS_DAP_EARG;
+  uint64_t list = 0;
+  for (uint32_t r = 0; r < n; r++) {
+    if (status[r]) continue;
+    if (ct_len[r] > ct_stride) return JANUS_DAP_EARG;
+    list += (uint64_t)REQ_FIXED + psl + enc_len + ps_len + ct_len[r];
+  }
+  if (list > 0xFFFFFFFFull) return JANUS_DAP_ETOOLONG;
+  size_t o = req_hdr_put(out, ap, apl, qt, bid);
+  put_be32(out + o, (uint32_t)list);
+  o += 4;
+  uint32_t k = 0;
+  for (uint32_t r = 0; r < n; r++) {
+    if (status[r]) {
+      index[r] = JANUS_DAP_INDEX_NONE;
+      continue;
+    }
+    index[r] = k++;
+    memcpy(out + o, ids + 16 * (size_t)r, 16);
+    put_be32(out + o + 16, (uint32_t)(times[r] >> 32));
+    put_be32(out + o + 20, (uint32_t)times[r]);
+    put_be32(out + o + 24, psl);
+    o += 28;
+    if (psl) memcpy(out + o, pub + (size_t)psl * r, psl);
+    o += psl;
+    out[o] = cfg[r];
+    out[o + 1] = (uint8_t)(enc_len >> 8);
+    out[o + 2] = (uint8_t)enc_len;
+    o += 3;
+    if (enc_len) memcpy(out + o, enc + (size_t)enc_len * r, enc_len);
+    o += enc_len;
+    put_be32(out + o, ct_len[r]);
+    o += 4;
+    if (ct_len[r]) memcpy(out + o, ct + (size_t)ct_stride * r, ct_len[r]);
+    o += ct_len[r];
+    put_be32(out + o, 5 + ps_len);
+    out[o + 4] = 0;  // PingPongMessage::Initialize
+    put_be32(out + o + 5, ps_len);
+    o += 9;
+    if (ps_len) memcpy(out + o, ps + (size_t)ps_len * r, ps_len);
+    o += ps_len;
+  }
+  *n_included = k;
+  return (int64_t)o;
+}
+
+int janus_dap_agg_init_req_encode_device(uint32_t n, const uint8_t* ap, uint32_t apl, uint8_t qt,
+                                         const uint8_t* bid, const uint8_t* d_ids,
+                                         const uint64_t* d_times, const uint8_t* d_pub,
+                                         uint32_t psl, const uint8_t* d_cfg, const uint8_t* d_enc,
+                                         uint32_t enc_len, const uint8_t* d_ct,
+                                         const uint32_t* d_ct_len, uint32_t ct_stride,
+                                         const uint8_t* d_ps, uint32_t ps_len,
+                                         const uint8_t* d_status, uint8_t* d_out,
+                                         uint64_t* d_out_len, uint32_t* d_index,
+                                         uint32_t* d_n_included, uint32_t* d_err, void* d_scratch,
+                                         void* stream) {
+  if (!d_out || !d_out_len || !d_n_included || !d_err || !d_scratch ||
+      ((uintptr_t)d_scratch & 7u) || apl > JANUS_DAP_AGG_PARAM_MAX ||
+      !req_args_ok(n, ap, apl, qt, bid, psl, enc_len, ct_stride, ps_len))
+    return JANUS_DAP_EARG;
+  if (n && (!d_ids || !d_times || !d_cfg || !d_ct_len || !d_status || !d_index ||
+            (psl && !d_pub) || (enc_len && !d_enc) || (ct_stride && !d_ct) || (ps_len && !d_ps)))
+    return JANUS_DAP_EARG;
+  const int dev = device_of(d_out);
+  if (dev < 0) return JANUS_DAP_EARG;
+  DeviceGuard guard(dev);
+  DCHK(guard.rc);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t nb = (n + REQ_CHUNK - 1) / REQ_CHUNK;
+  ReqHdr h;
+  memset(&h, 0, sizeof(h));
+  h.len = (uint32_t)req_hdr_put(h.b, ap, apl, qt, bid) + 4;
+  ReqArgs a{};
+  a.n = n;
+  a.psl = psl;
+  a.enc_len = enc_len;
+  a.ct_stride = ct_stride;
+  a.ps_len = ps_len;
+  a.ids = d_ids;
+  a.pub = d_pub;
+  a.cfg = d_cfg;
+  a.enc = d_enc;
+  a.ct = d_ct;
+  a.ps = d_ps;
+  a.status = d_status;
+  a.times = d_times;
+  a.ct_len = d_ct_len;
+  a.blk_bytes = (uint64_t*)d_scratch;
+  a.blk_cnt = (uint32_t*)(a.blk_bytes + nb + 1);
+  a.rel = a.blk_cnt + nb + 1;
+  a.out = d_out;
+  a.out_len = d_out_len;
+  a.index = d_index;
+  a.n_included = d_n_included;
+  a.err = d_err;
+  DCHK(hipMemsetAsync(d_err, 0, 8, st));
+  if (n) {
+    k_req_count<<<nb, 256, 0, st>>>(a);
+    DCHK(hipGetLastError());
+  }
+  k_req_scan<<<1, 1024, 0, st>>>(nb, a, h);
+  DCHK(hipGetLastError());
+  if (n) {
+    k_req_write<<<(n + REQ_SUB - 1) / REQ_SUB, 256, 0, st>>>(a, h.len);
+    DCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+int janus_dap_agg_job_resp_unpack_host(uint32_t n, const uint32_t* index, const uint8_t* ids,
+                                       uint32_t n_included, const uint8_t* body, size_t body_len,
+                                       uint32_t pml, uint8_t* msgs, uint8_t* perr) {
+  if (!body || n_included > n || (n && (!index || !ids || !perr || (pml && !msgs))))
+    return JANUS_DAP_EARG;
+  if (body_len < 4) return JANUS_DAP_RESP_ELISTLEN;
+  const uint64_t list = be32(body);
+  if (4 + list > body_len) return JANUS_DAP_RESP_ELISTLEN;
+  if (4 + list < body_len) return JANUS_DAP_RESP_ETRAILING;
+  // the whole message decodes before the driver looks at it: count the records first
+  const size_t end = body_len;
+  uint64_t count = 0;
+  for (size_t o = 4; o < end; count++) {
+    if (o + 17 > end) return JANUS_DAP_RESP_EMALFORMED;
+    const uint8_t ty = body[o + 16];
+    if (ty == 1) {
+      o += 17;
+    } else if (ty == 2) {
+      if (o + 18 > end) return JANUS_DAP_RESP_EMALFORMED;
+      if (body[o + 17] > 9) return JANUS_DAP_RESP_EREJECT_CODE;
+      o += 18;
+    } else if (ty == 0) {
+      if (o + 21 > end) return JANUS_DAP_RESP_EMALFORMED;
+      const uint64_t ml = be32(body + o + 17);
+      if (o + 21 + ml > end || !pingpong_wellformed(body + o + 21, ml))
+        return JANUS_DAP_RESP_EMALFORMED;
+      o += 21 + ml;
+    } else {
+      return JANUS_DAP_RESP_EMALFORMED;
+    }
+  }
+  if (count != n_included) return JANUS_DAP_RESP_ECOUNT;
+  // the row of each position of the request (index[] inverted)
+  std::vector<uint32_t> row(n_included, JANUS_DAP_INDEX_NONE);
+  for (uint32_t r = 0; r < n; r++) {
+    if (index[r] == JANUS_DAP_INDEX_NONE) continue;
+    if (index[r] >= n_included || row[index[r]] != JANUS_DAP_INDEX_NONE) return JANUS_DAP_EARG;
+    row[index[r]] = r;
+  }
+  if (pml) memset(msgs, 0, (size_t)n * pml);
+  if (n) memset(perr, 0xFF, n);
+  size_t o = 4;
+  for (uint32_t j = 0; j < n_included; j++) {
+    const uint32_t r = row[j];
+    if (r == JANUS_DAP_INDEX_NONE) return JANUS_DAP_EARG;
+    if (memcmp(body + o, ids + 16 * (size_t)r, 16)) return JANUS_DAP_RESP_EID;
+    const uint8_t ty = body[o + 16];
+    if (ty == 1) {
+      perr[r] = 5;  // VdafPrepError: a Prio3 leader is not finished before the helper's message
+      o += 17;
+    } else if (ty == 2) {
+      perr[r] = body[o + 17];
+      o += 18;
+    } else {
+      const uint32_t ml = be32(body + o + 17);
+      const uint8_t* m = body + o + 21;
+      if (m[0] == 2 && ml == 5 + (uint64_t)pml) {
+        if (pml) memcpy(msgs + (size_t)pml * r, m + 5, pml);
+      } else {
+        perr[r] = 5;  // leader_continued fails: PeerMessageMismatch / a prepare message that
+      }               // does not decode (handle_ping_pong_error -> VdafPrepError)
+      o += 21 + (size_t)ml;
+    }
+  }
+  return 0;
+}
+
+int janus_dap_agg_job_resp_unpack_device(uint32_t n, const uint32_t* d_index, const uint8_t* d_ids,
+                                         uint32_t n_included, const uint8_t* d_body,
+                                         size_t body_len, uint32_t pml, uint8_t* d_msgs,
+                                         uint8_t* d_perr, uint32_t* d_flags, void* d_scratch,
+                                         void* stream) {
+  if (!d_body || !d_flags || !d_scratch || ((uintptr_t)d_scratch & 3u) || n_included > n ||
+      body_len > 4ull + 0xFFFFFFFFull ||
+      (n && (!d_index || !d_ids || !d_perr || (pml && !d_msgs))))
+    return JANUS_DAP_EARG;
+  const int dev = device_of(d_flags);
+  if (dev < 0) return JANUS_DAP_EARG;
+  DeviceGuard guard(dev);
+  DCHK(guard.rc);
+  hipStream_t st = (hipStream_t)stream;
+  DCHK(hipMemsetAsync(d_flags, 0, 4, st));
+  RunpArgs a{};
+  a.body = d_body;
+  a.body_len = body_len;
+  a.n = n;
+  a.n_included = n_included;
+  a.pml = pml;
+  a.index = d_index;
+  a.ids = d_ids;
+  a.msgs = d_msgs;
+  a.perr = d_perr;
+  a.flags = d_flags;
+  a.walked = (uint32_t*)d_scratch;
+  a.off = a.walked + 1;
+  a.kind = (uint8_t*)(a.off + n_included);
+  k_runp_index<<<1, 1024, 0, st>>>(a);
+  DCHK(hipGetLastError());
+  if (n) {
+    k_runp_check<<<(n + 255) / 256, 256, 0, st>>>(a);
+    DCHK(hipGetLastError());
+    const uint64_t words = ((uint64_t)n * pml + 3) / 4;
+    if (words) {
+      k_runp_gather<<<(uint32_t)((words + 255) / 256), 256, 0, st>>>(a);
+      DCHK(hipGetLastError());
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """Python mirror of the DAP-09 marshaling around the device calls (include/janus_dap.h),
 SURVEY 8(f) row 3: AggregationJobInitializeReq body -> SoA buffers for the HPKE opener and the
-prio3 engine, and their outputs -> the AggregationJobResp body (helper init step)."""
+prio3 engine, and their outputs -> the AggregationJobResp body (helper init step); and the
+leader's two opposite directions: its SoA buffers -> the request body, the response body -> the
+prepare messages and per-report errors its prepare_next reads."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,6 +15,10 @@ DAP_EXPORTED_SYMBOLS = (
     "janus_dap_agg_init_scan", "janus_dap_agg_init_scan_ex", "janus_dap_agg_init_unpack_device",
     "janus_dap_agg_init_unpack_host", "janus_dap_agg_job_resp_max_len",
     "janus_dap_agg_job_resp_encode_device", "janus_dap_agg_job_resp_encode_host",
+    # leader side
+    "janus_dap_agg_init_req_max_len", "janus_dap_agg_init_req_encode_host",
+    "janus_dap_agg_init_req_encode_device", "janus_dap_agg_job_resp_unpack_host",
+    "janus_dap_agg_job_resp_unpack_device",
 )
 NO_ERROR = 0xFF  # prepare_error value meaning "no DAP-level error for this report"
 
@@ -47,6 +53,17 @@ def _lib():
                                                            vp]
         L.janus_dap_agg_job_resp_encode_host.argtypes = [u32, vp, vp, vp, vp, u32, vp]
         L.janus_dap_agg_job_resp_encode_host.restype = C.c_int64
+        u8 = C.c_uint8
+        L.janus_dap_agg_init_req_max_len.argtypes = [u32, u32, u8, u32, u32, u32, u32]
+        L.janus_dap_agg_init_req_max_len.restype = C.c_size_t
+        req = [u32, vp, u32, u8, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, u32, vp]
+        L.janus_dap_agg_init_req_encode_host.argtypes = req + [vp, vp, vp]
+        L.janus_dap_agg_init_req_encode_host.restype = C.c_int64
+        L.janus_dap_agg_init_req_encode_device.argtypes = req + [vp, vp, vp, vp, vp, vp, vp]
+        L.janus_dap_agg_job_resp_unpack_host.argtypes = [u32, vp, vp, u32, vp, C.c_size_t, u32, vp,
+                                                         vp]
+        L.janus_dap_agg_job_resp_unpack_device.argtypes = [u32, vp, vp, u32, vp, C.c_size_t, u32,
+                                                           vp, vp, vp, vp, vp]
         _bound = True
     return L
 
@@ -170,3 +187,220 @@ def encode_resp_device(report_ids, prepare_error, prio3_status, prep_msgs, prep_
     if rc:
         raise RuntimeError(f"janus_dap_agg_job_resp_encode_device failed (rc={rc})")
     return out, ln
+
+
+# ---- leader side: encode the request, decode the response ----------------------------------
+INDEX_NONE = 0xFFFFFFFF  # index[r] of a report that is not in the request
+VDAF_PREP_ERROR = 5      # DAP PrepareError::VdafPrepError
+AGG_PARAM_MAX = 256      # device form (JANUS_DAP_AGG_PARAM_MAX)
+RESP_IRREGULAR, RESP_LISTLEN, RESP_TRAILING, RESP_MALFORMED = 1, 2, 4, 8
+RESP_REJECT_CODE, RESP_COUNT, RESP_ID = 16, 32, 64
+RESP_ERRORS = {-3: "the list length runs past the body", -4: "bytes after the list",
+               -5: "a PrepareResp or its PingPongMessage does not decode",
+               -6: "Reject with a PrepareError code above 9",
+               -7: "the record count is not the request's",
+               -8: "a record's report ID is not the expected one"}
+
+
+class RespError(ValueError):
+    """The whole AggregationJobResp is rejected; ``code`` is the JANUS_DAP_RESP_E* value."""
+
+    def __init__(self, code):
+        super().__init__(f"AggregationJobResp rejected: {RESP_ERRORS.get(code, code)} (rc={code})")
+        self.code = code
+
+
+def leader_outcome(leader_status, prepare_error, next_status):
+    """Per-report outcome of the leader's init step, as prepare_error() is for the helper:
+    NO_ERROR for a report that finished (it is accumulated), else the DAP PrepareError it fails
+    with -- VdafPrepError when leader_initialized failed (leader_status != 0,
+    aggregation_job_driver.rs:430-437), the helper's error (prepare_error from the response
+    decode, :735-751), VdafPrepError when leader_continued failed (next_status != 0, :708-710).
+    numpy arrays or torch tensors."""
+    try:
+        import torch
+        if isinstance(leader_status, torch.Tensor):
+            fail = torch.full_like(prepare_error, VDAF_PREP_ERROR)
+            out = torch.where((prepare_error == NO_ERROR) & (next_status != 0), fail,
+                              prepare_error)
+            return torch.where(leader_status != 0, fail, out)
+    except ImportError:
+        pass
+    ls, ns = np.asarray(leader_status), np.asarray(next_status)
+    pe = np.asarray(prepare_error, np.uint8)
+    out = np.where((pe == NO_ERROR) & (ns != 0), VDAF_PREP_ERROR, pe)
+    return np.where(ls != 0, VDAF_PREP_ERROR, out).astype(np.uint8)
+
+
+def _req_header_check(agg_param, query_type, batch_id):
+    if query_type not in (1, 2):
+        raise ValueError("query_type must be 1 (TimeInterval) or 2 (FixedSize)")
+    if (query_type == 2) != (batch_id is not None) or (batch_id is not None and
+                                                       len(batch_id) != 32):
+        raise ValueError("FixedSize takes a 32-byte batch_id, TimeInterval none")
+    return np.frombuffer(bytes(agg_param), np.uint8), \
+        None if batch_id is None else np.frombuffer(bytes(batch_id), np.uint8)
+
+
+def _req_shapes(n, rows, vecs):
+    """rows: name -> 2-D [n, w] array / tensor (None: width 0); vecs: name -> 1-D [n]."""
+    for k, v in rows.items():
+        if v is not None and (v.ndim != 2 or v.shape[0] != n):
+            raise ValueError(f"{k} must be [{n}, width], not {tuple(v.shape)}")
+    for k, v in vecs.items():
+        if tuple(v.shape) != (n,):
+            raise ValueError(f"{k} must be [{n}], not {tuple(v.shape)}")
+    if rows["report_ids"].shape[1] != 16:
+        raise ValueError("report_ids must be [n, 16]")
+    if rows["enc"].shape[1] > 0xFFFF:
+        raise ValueError("enc is u16-prefixed")
+
+
+def encode_req_host(agg_param: bytes, query_type: int, batch_id, report_ids, times,
+                    public_shares, config_ids, enc, ct, ct_len, prep_shares, leader_status):
+    """AggregationJobInitializeReq of the reports with leader_status 0 (host buffers).
+    Returns (body bytes, index uint32 [n], n_included)."""
+    ap, bid = _req_header_check(agg_param, query_type, batch_id)
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    ids, tm, cfg = c(report_ids, np.uint8), c(times, np.uint64), c(config_ids, np.uint8)
+    pub = None if public_shares is None or np.shape(public_shares)[1] == 0 else \
+        c(public_shares, np.uint8)
+    e, t, cl = c(enc, np.uint8), c(ct, np.uint8), c(ct_len, np.uint32)
+    ps, st = c(prep_shares, np.uint8), c(leader_status, np.uint8)
+    n = ids.shape[0]
+    _req_shapes(n, dict(report_ids=ids, public_shares=pub, enc=e, ct=t, prep_shares=ps),
+                dict(times=tm, config_ids=cfg, ct_len=cl, leader_status=st))
+    if ((st == 0) & (cl > t.shape[1])).any():
+        raise ValueError("a ct_len is above the ct row length")
+    psl = 0 if pub is None else pub.shape[1]
+    L = _lib()
+    out = np.zeros(L.janus_dap_agg_init_req_max_len(n, len(ap), query_type, psl, e.shape[1],
+                                                    t.shape[1], ps.shape[1]), np.uint8)
+    index = np.zeros(n, np.uint32)
+    ninc = C.c_uint32(0)
+    ln = L.janus_dap_agg_init_req_encode_host(
+        n, _np_ptr(ap), len(ap), query_type, _np_ptr(bid), _np_ptr(ids), _np_ptr(tm), _np_ptr(pub),
+        psl, _np_ptr(cfg), _np_ptr(e), e.shape[1], _np_ptr(t), _np_ptr(cl), t.shape[1], _np_ptr(ps),
+        ps.shape[1], _np_ptr(st), _np_ptr(out), _np_ptr(index), C.byref(ninc))
+    if ln == -3:
+        raise OverflowError("the PrepareInit list does not fit its u32 length prefix")
+    if ln < 0:
+        raise ValueError(f"janus_dap_agg_init_req_encode_host failed (rc={ln})")
+    return out[:ln].tobytes(), index, ninc.value
+
+
+def _dev_tensor(name, t, esize, dev):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor on {dev}")
+    if t.element_size() != esize:
+        raise ValueError(f"{name} must have {esize}-byte elements")
+    return t
+
+
+def encode_req_device(agg_param: bytes, query_type: int, batch_id, report_ids, times,
+                      public_shares, config_ids, enc, ct, ct_len, prep_shares, leader_status,
+                      stream=None):
+    """Device form on torch tensors of one GPU (times: 8-byte, ct_len: 4-byte integers; ct /
+    ct_len as HpkeSealer.seal_input_shares_device writes them).  Returns a dict of tensors:
+    out (uint8, the body in its first out_len bytes), out_len (int64 [1]), index (int32 [n],
+    -1 = left out), n_included (int32 [1]), err (int32 [2]: reports left out for a ct_len above
+    the row length; 1 if the list does not fit a u32).  No host synchronisation."""
+    import torch
+    ap, bid = _req_header_check(agg_param, query_type, batch_id)
+    if len(ap) > AGG_PARAM_MAX:
+        raise ValueError(f"the device form takes up to {AGG_PARAM_MAX} aggregation parameter bytes")
+    dev = report_ids.device
+    if dev.type != "cuda":
+        raise ValueError("encode_req_device takes GPU tensors")
+    n = report_ids.shape[0]
+    pub = None if public_shares is None or public_shares.shape[1] == 0 else public_shares
+    rows = dict(report_ids=report_ids, public_shares=pub, enc=enc, ct=ct, prep_shares=prep_shares)
+    vecs = dict(times=times, config_ids=config_ids, ct_len=ct_len, leader_status=leader_status)
+    for k, v in rows.items():
+        if v is not None and v.shape[1]:
+            _dev_tensor(k, v, 1, dev)
+    for k, v in vecs.items():
+        _dev_tensor(k, v, 8 if k == "times" else 4 if k == "ct_len" else 1, dev)
+    _req_shapes(n, rows, vecs)
+    psl = 0 if pub is None else pub.shape[1]
+    L = _lib()
+    cap = L.janus_dap_agg_init_req_max_len(n, len(ap), query_type, psl, enc.shape[1], ct.shape[1],
+                                           prep_shares.shape[1])
+    res = dict(out=torch.empty(cap, dtype=torch.uint8, device=dev),
+               out_len=torch.zeros(1, dtype=torch.int64, device=dev),
+               index=torch.empty(n, dtype=torch.int32, device=dev),
+               n_included=torch.zeros(1, dtype=torch.int32, device=dev),
+               err=torch.zeros(2, dtype=torch.int32, device=dev))
+    scratch = torch.empty((n + 1) // 2 + 2 * (n // 256 + 2), dtype=torch.int64, device=dev)
+    w = lambda t: _tptr(t) if t is not None and t.shape[-1] else None  # noqa: E731
+    rc = L.janus_dap_agg_init_req_encode_device(
+        n, _np_ptr(ap), len(ap), query_type, _np_ptr(bid), _tptr(report_ids), _tptr(times), w(pub),
+        psl, _tptr(config_ids), w(enc), enc.shape[1], w(ct), _tptr(ct_len), ct.shape[1],
+        w(prep_shares), prep_shares.shape[1], _tptr(leader_status), _tptr(res["out"]),
+        _tptr(res["out_len"]), _tptr(res["index"]), _tptr(res["n_included"]), _tptr(res["err"]),
+        _tptr(scratch), _stream(stream, dev.index or 0))
+    if rc:
+        raise RuntimeError(f"janus_dap_agg_init_req_encode_device failed (rc={rc})")
+    return res
+
+
+def unpack_resp_host(body: bytes, index, report_ids, n_included: int, prep_msg_len: int):
+    """The leader's decode of an AggregationJobResp body (host buffers): returns (prep_msgs
+    uint8 [n, prep_msg_len], prepare_error uint8 [n]) in the engine's row order; raises
+    RespError when the whole response is rejected."""
+    ids = np.ascontiguousarray(report_ids, np.uint8)
+    idx = np.ascontiguousarray(index).astype(np.int64).astype(np.uint32)
+    n = ids.shape[0]
+    if ids.shape != (n, 16) or idx.shape != (n,):
+        raise ValueError("report_ids must be [n, 16] and index [n]")
+    inc = idx[idx != INDEX_NONE]
+    if not 0 <= n_included <= n or len(inc) != n_included or \
+            sorted(inc.tolist()) != list(range(n_included)):
+        raise ValueError("index must number the n_included reports of the request 0 .. "
+                         "n_included - 1")
+    buf = np.frombuffer(bytes(body) + b"\0", np.uint8)
+    msgs = np.zeros((n, prep_msg_len), np.uint8)
+    pe = np.zeros(n, np.uint8)
+    rc = _lib().janus_dap_agg_job_resp_unpack_host(n, _np_ptr(idx), _np_ptr(ids), n_included,
+                                                   _np_ptr(buf), len(body), prep_msg_len,
+                                                   _np_ptr(msgs), _np_ptr(pe))
+    if rc in RESP_ERRORS:
+        raise RespError(rc)
+    if rc:
+        raise ValueError(f"janus_dap_agg_job_resp_unpack_host failed (rc={rc})")
+    return msgs, pe
+
+
+def unpack_resp_device(d_body, body_len: int, index, report_ids, n_included: int,
+                       prep_msg_len: int, stream=None):
+    """Device form: d_body is a uint8 tensor holding the body and at least 4 more bytes; index
+    (int32 [n], as encode_req_device returns it) and report_ids (uint8 [n, 16]) are tensors on
+    the same GPU.  Returns (prep_msgs [n, max(prep_msg_len, 1)], prepare_error [n], flags int32
+    [1]); a non-zero flags (RESP_* bits) means the outputs are incomplete: RESP_IRREGULAR alone
+    sends the body to unpack_resp_host, every other bit rejects the response."""
+    import torch
+    dev = d_body.device
+    if dev.type != "cuda":
+        raise ValueError("unpack_resp_device takes GPU tensors")
+    n = report_ids.shape[0]
+    _dev_tensor("d_body", d_body, 1, dev)
+    _dev_tensor("index", index, 4, dev)
+    _dev_tensor("report_ids", report_ids, 1, dev)
+    if tuple(report_ids.shape) != (n, 16) or tuple(index.shape) != (n,):
+        raise ValueError("report_ids must be [n, 16] and index [n]")
+    if not 0 <= n_included <= n:
+        raise ValueError("n_included must be within 0 .. n")
+    if body_len < 0 or d_body.numel() < body_len + 4:
+        raise ValueError("d_body must hold the body and 4 bytes of padding")
+    msgs = torch.empty((n, max(prep_msg_len, 1)), dtype=torch.uint8, device=dev)
+    pe = torch.empty(n, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(2 * (n_included + 2), dtype=torch.int32, device=dev)
+    rc = _lib().janus_dap_agg_job_resp_unpack_device(
+        n, _tptr(index), _tptr(report_ids), n_included, _tptr(d_body), body_len, prep_msg_len,
+        _tptr(msgs) if prep_msg_len else None, _tptr(pe), _tptr(flags), _tptr(scratch),
+        _stream(stream, dev.index or 0))
+    if rc:
+        raise RuntimeError(f"janus_dap_agg_job_resp_unpack_device failed (rc={rc})")
+    return msgs, pe, flags

@@ -752,13 +752,17 @@ class HelperEngine:
 
     def generate_sealed_reports_device(self, sealer, task_id: bytes, n: int, times, sk_e,
                                        seed: int = 1, first_index: int = 0,
-                                       with_taskprov_extension: bool = False, stream=None) -> dict:
+                                       with_taskprov_extension: bool = False, stream=None,
+                                       with_checks: bool = False,
+                                       with_leader_inputs: bool = False) -> dict:
         """``generate_reports_device`` followed, on the same stream, by
         ``sealer.seal_input_shares_device`` (janus_amd.hpke.HpkeSealer on this engine's GPU): what
         a helper actually receives.  The report IDs are the reports' nonces.  times [n] (8-byte
         integers) and sk_e [n, 32] (uint8, one ephemeral private key per report from the caller's
         CSPRNG) are torch tensors on the GPU.  Returns the client's dict plus enc [n, Nenc],
-        ct [n, stride], ct_len [n] (int32) and seal_status [n]."""
+        ct [n, stride], ct_len [n] (int32) and seal_status [n]; with_checks / with_leader_inputs
+        as for ``generate_reports_device`` (the measurements; the leader input shares a leader
+        engine's ``leader_prepare_init_device`` reads)."""
         import torch
         from .hpke import NSK_E, sealed_stride
         if len(task_id) != 32:
@@ -769,7 +773,9 @@ class HelperEngine:
             raise ValueError(f"times must be [{n}] and sk_e [{n}, {NSK_E}]")
         if self.sz.public_share_len not in (0, 32, 64):
             raise ValueError("the sealer takes public shares of 0, 32 or 64 bytes")
-        out = self.generate_reports_device(n, seed=seed, first_index=first_index, stream=stream)
+        out = self.generate_reports_device(n, seed=seed, first_index=first_index, stream=stream,
+                                           with_checks=with_checks,
+                                           with_leader_inputs=with_leader_inputs)
         dev = torch.device("cuda", self.device)
         out["enc"] = torch.empty((n, sealer.nenc), dtype=torch.uint8, device=dev)
         out["ct"] = torch.empty((n, sealed_stride(self.sz.helper_share_len,
