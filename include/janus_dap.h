@@ -227,6 +227,44 @@ int janus_dap_agg_job_resp_unpack_device(uint32_t n, const uint32_t* d_index,
                                          uint8_t* d_prepare_error, uint32_t* d_flags,
                                          void* d_scratch, void* stream);
 
+/* ---- Client side: the upload body -----------------------------------------------------------
+ * Report (lib.rs, struct Report) = ReportMetadata { report_id[16], time u64 }, u32-prefixed
+ * public share, HpkeCiphertext to the leader, HpkeCiphertext to the helper -- what
+ * Client::prepare_report returns (client/src/lib.rs:339-383) and the client PUTs to the leader.
+ * Every report is its own HTTP body, so the output is one row per report: out[n][out_stride] and
+ * out_len[n] (u32).  The ciphertext rows are those the sealer writes (enc[n][enc_len],
+ * ct[n][ct_stride] with ct_len[n]); no byte past a row's ct_len is read.  A report whose skip byte
+ * is non-zero (skip may be NULL), or one of whose ct_len is 0 or above its stride, is left out:
+ * out_len 0 and an all-zero row.  The bytes of a row past its report are zero.  out_stride below
+ * janus_dap_report_max_len(...) or an enc_len above 0xFFFF is JANUS_DAP_EARG.
+ * Device form: runs on `stream` of the GPU that owns d_out without host synchronisation; the
+ * calling thread's current device is left as it was.  Host form: returns the number of reports
+ * written (rows with out_len != 0) or JANUS_DAP_EARG.  The decoding direction (the leader's upload
+ * handler) is not provided. */
+size_t janus_dap_report_max_len(uint32_t public_share_len, uint32_t leader_enc_len,
+                                uint32_t leader_ct_stride, uint32_t helper_enc_len,
+                                uint32_t helper_ct_stride);
+int janus_dap_report_encode_device(uint32_t n, const uint8_t* d_report_ids, const uint64_t* d_times,
+                                   const uint8_t* d_public_shares, uint32_t public_share_len,
+                                   uint8_t leader_config_id, const uint8_t* d_leader_enc,
+                                   uint32_t leader_enc_len, const uint8_t* d_leader_ct,
+                                   const uint32_t* d_leader_ct_len, uint32_t leader_ct_stride,
+                                   uint8_t helper_config_id, const uint8_t* d_helper_enc,
+                                   uint32_t helper_enc_len, const uint8_t* d_helper_ct,
+                                   const uint32_t* d_helper_ct_len, uint32_t helper_ct_stride,
+                                   const uint8_t* d_skip, uint8_t* d_out, uint32_t out_stride,
+                                   uint32_t* d_out_len, void* stream);
+int64_t janus_dap_report_encode_host(uint32_t n, const uint8_t* report_ids, const uint64_t* times,
+                                     const uint8_t* public_shares, uint32_t public_share_len,
+                                     uint8_t leader_config_id, const uint8_t* leader_enc,
+                                     uint32_t leader_enc_len, const uint8_t* leader_ct,
+                                     const uint32_t* leader_ct_len, uint32_t leader_ct_stride,
+                                     uint8_t helper_config_id, const uint8_t* helper_enc,
+                                     uint32_t helper_enc_len, const uint8_t* helper_ct,
+                                     const uint32_t* helper_ct_len, uint32_t helper_ct_stride,
+                                     const uint8_t* skip, uint8_t* out, uint32_t out_stride,
+                                     uint32_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

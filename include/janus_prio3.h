@@ -369,6 +369,73 @@ int prio3_device_leader_prepare_next(prio3_engine* engine, uint32_t n, const uin
  * with n_segments == 1 finishes from them (the verdicts, the accept mask and out-of-range
  * segment ids are applied as corrections), any other accumulate reads the output shares. */
 
+/* ---- Client ---- */
+/* The client role of prio::vdaf: Prio3::shard on the caller's measurements (client/src/lib.rs:
+ * 339-341).  Per report r: d_measurements[r][SumVec: length, else 1] (u64), d_nonces[r][16] (the
+ * report ID) and d_rand[r][prio3_client_rand_len] from the caller's CSPRNG (the library draws no
+ * randomness, and a row must never be reused).  Randomness layout, prio's order, 16-byte seeds:
+ *   helper measurement share seed | helper proofs share seed |
+ *   [ helper blind | leader blind | ]  prove randomness seed
+ * -- the two blinds only for instances with joint randomness (Sum, SumVec, Histogram: joint_rand_len
+ * of prio3_sizes non-zero); without them (Count) the prove seed follows the two helper seeds.
+ * Outputs per report: d_public_shares[r][public_share_len] (may be NULL when that is 0),
+ * d_leader_input_shares[r][leader_input_share_len], d_helper_shares[r][helper_share_len] and
+ * d_status[r]: PRIO3_CLIENT_OK, or PRIO3_CLIENT_INVALID_MEASUREMENT for a measurement prio's
+ * encode_measurement rejects (Count: not 0 / 1; Sum, SumVec: an entry >= 2^bits; Histogram: an
+ * index >= length) -- its three rows are all zero and the other reports are not affected.
+ * Every XOF expansion is sampled exactly (rejection sampling as prio does; there is no "unusable"
+ * flag as in the synthetic generator below), the engine's verify key is not read, and nothing of
+ * the leader's prepare_init is computed.  Device pointers are 16-byte aligned.  Stream-ordered;
+ * the call does not wait for the device.
+ * PRIO3_SUMVEC_F64_MP and PRIO3_FPVEC_BOUNDED_L2 return PRIO3_EUNSUPPORTED from every entry point
+ * of this section (FPVec's circuit is a reconstruction and its fixed-point encoding needs a
+ * contract of its own); their seeded generators below stay. */
+enum { PRIO3_CLIENT_OK = 0, PRIO3_CLIENT_INVALID_MEASUREMENT = 1 };
+/* seed_size * (5 with joint randomness, else 3); 0 for parameters prio3_sizes rejects */
+int prio3_client_rand_len(const prio3_params* params);
+int prio3_client_shard_device(prio3_engine* engine, uint32_t n, const uint64_t* d_measurements,
+                              const uint8_t* d_nonces, const uint8_t* d_rand,
+                              uint8_t* d_public_shares, uint8_t* d_leader_input_shares,
+                              uint8_t* d_helper_shares, uint8_t* d_status, void* stream);
+/* The same with host buffers (blocking). */
+int prio3_client_shard_batch(prio3_engine* engine, uint32_t n, const uint64_t* measurements,
+                             const uint8_t* nonces, const uint8_t* rand, uint8_t* public_shares,
+                             uint8_t* leader_input_shares, uint8_t* helper_shares,
+                             uint8_t* status);
+
+/* Client::prepare_report (client/src/lib.rs:339-383) for a batch of one task, on one stream with
+ * no host round trip: each time rounded down to the task's time precision (t - t % precision,
+ * to_batch_interval_start), the shard above, one input share sealed to each aggregator -- the
+ * leader's with leader_sealer (info "dap-09 input share" || 0x01 || 0x02), the helper's with
+ * helper_sealer (... || 0x01 || 0x03), both over the same InputShareAad { task_id, metadata,
+ * public share } with the rounded time, each with its own caller-supplied ephemeral keys
+ * d_sk_e_leader / d_sk_e_helper [n][32] (janus_hpke.h, Seal) -- and the Report encode of
+ * janus_dap.h.  The client sends no extension (lib.rs:361); with_taskprov_extension adds the one
+ * empty taskprov extension to both plaintexts, as janus_hpke_seal_input_shares_device does.
+ * Outputs: d_reports[n][report_stride] with d_report_len[n] (u32), and d_status[n]: 0,
+ * PRIO3_CLIENT_INVALID_MEASUREMENT, or the sealer's JANUS_HPKE_SEAL_KEY_ERROR (0x40) /
+ * _LENGTH_ERROR (0x41), the shard's first, then the leader seal's; a report with a non-zero status
+ * has length 0 and a zero row.  report_stride >= prio3_client_report_stride(...), else
+ * PRIO3_EINVAL; also PRIO3_EINVAL: time_precision 0, a NULL sealer, a sealer bound to another GPU
+ * than the engine.  (A sealer exists only for the KEMs the seal supports: X25519 and P-256.)
+ * The intermediate shares and ciphertexts live in pooled device scratch; batches whose scratch
+ * does not fit in free memory run in sub-batches on the same stream. */
+struct janus_hpke_sealer;
+/* the row length that holds any Report of the instance and the two sealers' KEMs (0: invalid
+ * parameters or a NULL sealer) */
+int prio3_client_report_stride(const prio3_params* params,
+                               const struct janus_hpke_sealer* leader_sealer,
+                               const struct janus_hpke_sealer* helper_sealer,
+                               int with_taskprov_extension);
+int prio3_client_prepare_reports_device(
+    prio3_engine* engine, struct janus_hpke_sealer* leader_sealer,
+    struct janus_hpke_sealer* helper_sealer, uint32_t n, const uint8_t task_id[32],
+    uint64_t time_precision, const uint64_t* d_measurements, const uint8_t* d_report_ids,
+    const uint64_t* d_times, const uint8_t* d_rand, const uint8_t* d_sk_e_leader,
+    const uint8_t* d_sk_e_helper, uint8_t leader_config_id, uint8_t helper_config_id,
+    int with_taskprov_extension, uint8_t* d_reports, uint32_t report_stride,
+    uint32_t* d_report_len, uint8_t* d_status, void* stream);
+
 /* ---- Synthetic client (benchmarks and tests) ---- */
 /* Generates n honest reports on the device: the client's shard (prio Prio3::shard,
  * client/src/lib.rs:339-341) and the leader's prepare_init (agg_id 0,

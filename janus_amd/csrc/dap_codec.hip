@@ -477,6 +477,78 @@ __global__ __launch_bounds__(256) void k_req_write(ReqArgs a, uint32_t hdr_len) 
   }
 }
 
+// ---- client side: Report encode -------------------------------------------------------------
+// Report (messages/src/lib.rs, struct Report) = ReportMetadata { report_id[16], time u64 },
+// u32-prefixed public share, HpkeCiphertext to the leader, HpkeCiphertext to the helper; each
+// HpkeCiphertext { config_id u8, u16-prefixed enc, u32-prefixed payload }.  One report per output
+// row (every report is its own upload body).
+constexpr uint32_t REP_FIXED = 16 + 8 + 4 + 2 * (1 + 2 + 4);
+
+struct RepCt {  // one aggregator's ciphertext rows
+  const uint8_t *enc, *ct;
+  const uint32_t* ct_len;
+  uint32_t enc_len, ct_stride, cfg;
+};
+struct RepArgs {
+  uint32_t n, psl, out_stride;
+  const uint8_t *ids, *pub, *skip;
+  const uint64_t* times;
+  RepCt c[2];  // leader, helper
+  uint8_t* out;
+  uint32_t* out_len;
+};
+
+// byte k of one HpkeCiphertext (k < 7 + enc_len + cl)
+DEV uint32_t rep_ct_byte(const RepCt& c, uint32_t r, uint32_t cl, uint32_t k) {
+  if (k == 0) return c.cfg;
+  if (k < 3) return (c.enc_len >> (8 * (2 - k))) & 0xFFu;
+  k -= 3;
+  if (k < c.enc_len) return c.enc[(size_t)c.enc_len * r + k];
+  k -= c.enc_len;
+  if (k < 4) return (cl >> (8 * (3 - k))) & 0xFFu;
+  return c.ct[(size_t)c.ct_stride * r + (k - 4)];  // k - 4 < cl: nothing past ct_len is read
+}
+
+// byte k (k < the report's length) of report r; ll / hl = its two ct_len
+DEV uint32_t rep_byte(const RepArgs& a, uint32_t r, uint32_t ll, uint32_t hl, uint32_t k) {
+  if (k < 16) return a.ids[16 * (size_t)r + k];
+  if (k < 24) return (uint32_t)(a.times[r] >> (8 * (23 - k))) & 0xFFu;
+  if (k < 28) return (a.psl >> (8 * (27 - k))) & 0xFFu;
+  k -= 28;
+  if (k < a.psl) return a.pub[(size_t)a.psl * r + k];
+  k -= a.psl;
+  const uint32_t l0 = 7 + a.c[0].enc_len + ll;
+  if (k < l0) return rep_ct_byte(a.c[0], r, ll, k);
+  return rep_ct_byte(a.c[1], r, hl, k - l0);
+}
+
+// k_rep_write: one block per report, one lane per aligned dword of its output row (the row's first
+// and last bytes, which may share a dword with the neighbouring rows, are stored bytewise); the
+// row's bytes past the report are zero, and a report that is left out is a zero row of length 0.
+__global__ __launch_bounds__(256) void k_rep_write(RepArgs a) {
+  const uint32_t r = blockIdx.x, t = threadIdx.x;
+  const uint32_t ll = a.c[0].ct_len[r], hl = a.c[1].ct_len[r];
+  const bool out_ok = !(a.skip && a.skip[r]) && ll != 0 && ll <= a.c[0].ct_stride && hl != 0 &&
+                      hl <= a.c[1].ct_stride;
+  const uint32_t len = out_ok ? REP_FIXED + a.psl + a.c[0].enc_len + ll + a.c[1].enc_len + hl : 0u;
+  if (t == 0) a.out_len[r] = len;
+  uint8_t* row = a.out + (size_t)a.out_stride * r;
+  const uint32_t mis = (uint32_t)((uintptr_t)row & 3u);
+  const uint32_t nd = (mis + a.out_stride + 3) >> 2;
+  for (uint32_t j = t; j < nd; j += 256) {
+    const int64_t x0 = 4 * (int64_t)j - mis;  // dword j = row bytes [x0, x0 + 4)
+    const bool whole = x0 >= 0 && x0 + 4 <= (int64_t)a.out_stride;
+    uint32_t v = 0;
+    for (int b = 0; b < 4; b++) {
+      const int64_t x = x0 + b;
+      if (x < 0 || x >= (int64_t)a.out_stride) continue;
+      const uint32_t byte = (uint32_t)x < len ? rep_byte(a, r, ll, hl, (uint32_t)x) : 0u;
+      if (whole) v |= byte << (8 * b); else row[x] = (uint8_t)byte;
+    }
+    if (whole) *(uint32_t*)(row + x0) = v;
+  }
+}
+
 // ---- leader side: AggregationJobResp decode -----------------------------------------------
 // The three regular PrepareResp shapes: Continue { Finish { prep_msg[pml] } } = 26 + pml bytes,
 // Finished = 17, Reject(e) = 18.  Record offsets depend on every earlier record, so one workgroup
@@ -1240,6 +1312,108 @@ int janus_dap_agg_job_resp_unpack_device(uint32_t n, const uint32_t* d_index, co
     }
   }
   return 0;
+}
+
+// ---- client side ----------------------------------------------------------------------------
+namespace {
+bool rep_args_ok(uint32_t psl, uint32_t lenc, uint32_t lstride, uint32_t henc, uint32_t hstride,
+                 uint32_t out_stride) {
+  if (lenc > 0xFFFF || henc > 0xFFFF) return false;
+  const uint64_t max_len = (uint64_t)REP_FIXED + psl + lenc + lstride + henc + hstride;
+  return max_len < (1ull << 31) && out_stride >= max_len;
+}
+}  // namespace
+
+size_t janus_dap_report_max_len(uint32_t psl, uint32_t lenc, uint32_t lstride, uint32_t henc,
+                                uint32_t hstride) {
+  return (size_t)REP_FIXED + psl + lenc + lstride + henc + hstride;
+}
+
+int janus_dap_report_encode_device(uint32_t n, const uint8_t* d_ids, const uint64_t* d_times,
+                                   const uint8_t* d_pub, uint32_t psl, uint8_t leader_config_id,
+                                   const uint8_t* d_lenc, uint32_t lenc, const uint8_t* d_lct,
+                                   const uint32_t* d_lct_len, uint32_t lstride,
+                                   uint8_t helper_config_id, const uint8_t* d_henc, uint32_t henc,
+                                   const uint8_t* d_hct, const uint32_t* d_hct_len,
+                                   uint32_t hstride, const uint8_t* d_skip, uint8_t* d_out,
+                                   uint32_t out_stride, uint32_t* d_out_len, void* stream) {
+  if (!rep_args_ok(psl, lenc, lstride, henc, hstride, out_stride)) return JANUS_DAP_EARG;
+  if (n == 0) return 0;
+  if (!d_ids || !d_times || !d_lct_len || !d_hct_len || !d_out || !d_out_len || (psl && !d_pub) ||
+      (lenc && !d_lenc) || (henc && !d_henc) || (lstride && !d_lct) || (hstride && !d_hct))
+    return JANUS_DAP_EARG;
+  const int dev = device_of(d_out);
+  if (dev < 0) return JANUS_DAP_EARG;
+  DeviceGuard guard(dev);
+  DCHK(guard.rc);
+  RepArgs a{};
+  a.n = n;
+  a.psl = psl;
+  a.out_stride = out_stride;
+  a.ids = d_ids;
+  a.pub = d_pub;
+  a.skip = d_skip;
+  a.times = d_times;
+  a.c[0] = RepCt{d_lenc, d_lct, d_lct_len, lenc, lstride, leader_config_id};
+  a.c[1] = RepCt{d_henc, d_hct, d_hct_len, henc, hstride, helper_config_id};
+  a.out = d_out;
+  a.out_len = d_out_len;
+  k_rep_write<<<n, 256, 0, (hipStream_t)stream>>>(a);
+  DCHK(hipGetLastError());
+  return 0;
+}
+
+int64_t janus_dap_report_encode_host(uint32_t n, const uint8_t* ids, const uint64_t* times,
+                                     const uint8_t* pub, uint32_t psl, uint8_t leader_config_id,
+                                     const uint8_t* lenc_rows, uint32_t lenc, const uint8_t* lct,
+                                     const uint32_t* lct_len, uint32_t lstride,
+                                     uint8_t helper_config_id, const uint8_t* henc_rows,
+                                     uint32_t henc, const uint8_t* hct, const uint32_t* hct_len,
+                                     uint32_t hstride, const uint8_t* skip, uint8_t* out,
+                                     uint32_t out_stride, uint32_t* out_len) {
+  if (!rep_args_ok(psl, lenc, lstride, henc, hstride, out_stride)) return JANUS_DAP_EARG;
+  if (n == 0) return 0;
+  if (!ids || !times || !lct_len || !hct_len || !out || !out_len || (psl && !pub) ||
+      (lenc && !lenc_rows) || (henc && !henc_rows) || (lstride && !lct) || (hstride && !hct))
+    return JANUS_DAP_EARG;
+  const uint8_t cfg[2] = {leader_config_id, helper_config_id};
+  const uint8_t* encs[2] = {lenc_rows, henc_rows};
+  const uint8_t* cts[2] = {lct, hct};
+  const uint32_t* cls[2] = {lct_len, hct_len};
+  const uint32_t enc_len[2] = {lenc, henc}, stride[2] = {lstride, hstride};
+  int64_t emitted = 0;
+  for (uint32_t r = 0; r < n; r++) {
+    uint8_t* row = out + (size_t)out_stride * r;
+    memset(row, 0, out_stride);
+    out_len[r] = 0;
+    if ((skip && skip[r]) || lct_len[r] == 0 || lct_len[r] > lstride || hct_len[r] == 0 ||
+        hct_len[r] > hstride)
+      continue;
+    size_t o = 0;
+    memcpy(row, ids + 16 * (size_t)r, 16);
+    put_be32(row + 16, (uint32_t)(times[r] >> 32));
+    put_be32(row + 20, (uint32_t)times[r]);
+    put_be32(row + 24, psl);
+    o = 28;
+    if (psl) memcpy(row + o, pub + (size_t)psl * r, psl);
+    o += psl;
+    for (int c = 0; c < 2; c++) {
+      const uint32_t cl = cls[c][r];
+      row[o] = cfg[c];
+      row[o + 1] = (uint8_t)(enc_len[c] >> 8);
+      row[o + 2] = (uint8_t)enc_len[c];
+      o += 3;
+      if (enc_len[c]) memcpy(row + o, encs[c] + (size_t)enc_len[c] * r, enc_len[c]);
+      o += enc_len[c];
+      put_be32(row + o, cl);
+      o += 4;
+      memcpy(row + o, cts[c] + (size_t)stride[c] * r, cl);
+      o += cl;
+    }
+    out_len[r] = (uint32_t)o;
+    emitted++;
+  }
+  return emitted;
 }
 
 }  // extern "C"

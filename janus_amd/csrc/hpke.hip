@@ -1502,6 +1502,9 @@ struct janus_hpke_sealer {
   std::mutex mu;              // P.task
 };
 
+int hpke_sealer_device(const janus_hpke_sealer* s) { return s->device; }
+size_t hpke_sealer_nenc(const janus_hpke_sealer* s) { return kem_nenc((uint16_t)s->P.kem); }
+
 static int seal_args_ok(uint32_t ct_stride, uint32_t pt_stride, uint32_t aad_stride) {
   return ct_stride >= 16 && ct_stride % 16 == 0 && pt_stride % 16 == 0 && aad_stride % 16 == 0;
 }

@@ -18,6 +18,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/janus_dap.h"
+#include "../../include/janus_hpke.h"
 #include "prio3_common.h"
 #include "prio3_runtime.h"
 #include "prio3_mp64_xof.h"
@@ -390,6 +392,157 @@ __global__ __launch_bounds__(64) void k_gen(DevParams p, uint64_t seed, uint64_t
     }
   }
   if (go.flags) go.flags[r] = (uint8_t)flag;
+}
+
+// ====================================================================================
+// The client role: prio Prio3::shard (VDAF-08 7.2.1) on caller-supplied measurements, nonces and
+// randomness (prio3_client_shard_device).  One report per lane on the generator's SoA scratch, with
+// its prove_lane / jr_part_scratch / seed_of; no verify key, no query, no leader prepare_init.
+// Every expansion is sampled exactly: k_shard runs the block-wise expand_to and marks a report any
+// of whose four expansions (helper measurement share, joint randomness, prove randomness, helper
+// proofs share) meets a candidate >= p -- or every report, with the engine's force_slow_path; one
+// deferred launch per call, k_shard_redo, shards the marked reports through the byte-level
+// rejection sampler bx_expand (as k_slow_redo does for the helper).
+// ====================================================================================
+struct ShardIn {
+  const uint64_t* meas;  // [n][SumVec: length, else 1]
+  const uint8_t* nonces;  // [n][16]
+  const uint8_t* rand;    // [n][16 * (5 with joint randomness, else 3)]
+};
+struct ShardOut {
+  uint8_t *pub, *leader, *helper, *status;
+};
+
+// status byte of a report the fast launch left to the rejection-sampling launch (never returned)
+constexpr uint8_t SHARD_REDO = 0xFF;
+
+// Report r on scratch column c.  SLOW = false: the block-wise expansions; a report that meets a
+// candidate >= p in any of them (or every report, with force_slow_path) is marked SHARD_REDO and
+// left.  SLOW = true: the same through the byte-level rejection sampler, which is always exact.
+template <class F, bool SLOW>
+DEV void shard_report(const DevParams& p, const GenScratch& gs, const ShardIn& in,
+                      const ShardOut& out, uint32_t r, uint32_t c, typename F::T invP,
+                      typename F::T inv2P) {
+  const size_t ld = p.ld;
+  const uint32_t M = p.meas_len, A = p.arity, PL = p.proof_len;
+  const bool JR = p.jr_len > 0;
+  const uint32_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1;
+  uint8_t* li = out.leader + (size_t)r * p.leader_share_len;
+  uint8_t* hs = out.helper + (size_t)r * p.helper_share_len;
+  uint8_t* pb = out.pub + (size_t)r * p.public_share_len;  // written only with joint randomness
+  // ---- encode_measurement: the field encoding into gs.meas, validated on the way ----
+  for (uint32_t e = 0; e < M; e++) F::store(gs.meas, (size_t)e * ld + c, F::zero());
+  bool valid = true;
+  for (uint32_t e = 0; e < mstride; e++) {
+    const uint64_t v = in.meas[(size_t)r * mstride + e];
+    switch (p.kind) {
+      case PRIO3_COUNT:
+        valid = valid && v <= 1;
+        F::store(gs.meas, c, F::from_u32((uint32_t)(v & 1)));
+        break;
+      case PRIO3_SUM:
+      case PRIO3_SUMVEC:
+        valid = valid && (p.bits >= 64 || (v >> p.bits) == 0);
+        for (uint32_t b = 0; b < p.bits; b++)
+          F::store(gs.meas, (size_t)(e * p.bits + b) * ld + c, F::from_u32((uint32_t)((v >> b) & 1)));
+        break;
+      default: {  // Histogram: the index's one-hot vector
+        const bool ok = v < p.length;
+        valid = valid && ok;
+        F::store(gs.meas, (size_t)(ok ? v : 0) * ld + c, ok ? F::one() : F::zero());
+        break;
+      }
+    }
+  }
+  if (!valid) {  // all three rows zero (every row length is a multiple of 8)
+    for (uint32_t k = 0; k < p.leader_share_len / 8; k++) ((uint64_t*)li)[k] = 0;
+    for (uint32_t k = 0; k < p.helper_share_len / 8; k++) ((uint64_t*)hs)[k] = 0;
+    if (JR)
+      for (uint32_t k = 0; k < p.public_share_len / 8; k++) ((uint64_t*)pb)[k] = 0;
+    out.status[r] = PRIO3_CLIENT_INVALID_MEASUREMENT;
+    return;
+  }
+  // ---- the caller's nonce and randomness: k_hm, k_hp, [k_hb, k_lb,] k_prove ----
+  uint32_t nonce[4], k_hm[4], k_hp[4], k_hb[4] = {0, 0, 0, 0}, k_lb[4] = {0, 0, 0, 0}, k_pr[4];
+  load16(in.nonces + 16 * (size_t)r, nonce);
+  const uint8_t* rnd = in.rand + (size_t)r * (JR ? 80 : 48);
+  load16(rnd, k_hm);
+  load16(rnd + 16, k_hp);
+  if (JR) {
+    load16(rnd + 32, k_hb);
+    load16(rnd + 48, k_lb);
+    load16(rnd + 64, k_pr);
+  } else {
+    load16(rnd + 32, k_pr);
+  }
+  // ---- the four expansions ----
+  uint32_t flag = SLOW ? 0u : p.force_slow;
+  auto expand = [&](const uint32_t* dst2, const uint32_t* seed, const uint8_t* binder, int blen,
+                    uint32_t n, void* base) {
+    if constexpr (SLOW)
+      bx_expand<F>(dst2, seed, binder, blen, n, base, ld, c);
+    else
+      expand_to<F>(p, dst2, seed, binder, blen, n, base, c, flag);
+  };
+  const uint8_t b1[1] = {1}, b2[2] = {1, 1};
+  uint32_t part0[4] = {0, 0, 0, 0}, part1[4] = {0, 0, 0, 0};
+  expand(p.dst[1], k_hm, b1, 1, M, gs.hm);
+  if (flag == 0) {  // (a rejected measurement share changes everything after it)
+    for (uint32_t e = 0; e < M; e++)
+      F::store(gs.lm, (size_t)e * ld + c,
+               F::sub(F::load(gs.meas, (size_t)e * ld + c), F::load(gs.hm, (size_t)e * ld + c)));
+    if (JR) {
+      uint32_t jseed[4];
+      jr_part_scratch<F>(p, k_hb, 1, nonce, gs.hm, c, part1);
+      jr_part_scratch<F>(p, k_lb, 0, nonce, gs.lm, c, part0);
+      const uint32_t zero[4] = {0, 0, 0, 0};
+      seed_of<F>(p, 6, zero, part0, part1, jseed);
+      expand(p.dst[3], jseed, b1, 1, p.jr_len, gs.jr);
+    }
+    expand(p.dst[4], k_pr, b1, 1, A, gs.prand);
+    expand(p.dst[2], k_hp, b2, 2, PL, gs.hp);
+  }
+  if (flag) {
+    out.status[r] = SHARD_REDO;
+    return;
+  }
+  prove_lane<F>(p, gs, gs.meas, gs.prand, gs.jr, gs.proof, c, invP, inv2P);
+  // ---- leader input share = enc(meas share) || enc(proof - helper proofs share) [|| k_blind] ----
+  for (uint32_t e = 0; e < M; e++) F::store(li, e, F::load(gs.lm, (size_t)e * ld + c));
+  for (uint32_t e = 0; e < PL; e++)
+    F::store(li + (size_t)M * F::ES, e,
+             F::sub(F::load(gs.proof, (size_t)e * ld + c), F::load(gs.hp, (size_t)e * ld + c)));
+  *(uint4*)hs = make_uint4(k_hm[0], k_hm[1], k_hm[2], k_hm[3]);
+  *(uint4*)(hs + 16) = make_uint4(k_hp[0], k_hp[1], k_hp[2], k_hp[3]);
+  if (JR) {
+    *(uint4*)(li + (size_t)(M + PL) * F::ES) = make_uint4(k_lb[0], k_lb[1], k_lb[2], k_lb[3]);
+    *(uint4*)(hs + 32) = make_uint4(k_hb[0], k_hb[1], k_hb[2], k_hb[3]);
+    *(uint4*)pb = make_uint4(part0[0], part0[1], part0[2], part0[3]);
+    *(uint4*)(pb + 16) = make_uint4(part1[0], part1[1], part1[2], part1[3]);
+  }
+  out.status[r] = PRIO3_CLIENT_OK;
+}
+
+// the fast launch: report r of the chunk on column r
+template <class F>
+__global__ __launch_bounds__(64) void k_shard(DevParams p, GenScratch gs, ShardIn in, ShardOut out,
+                                              typename F::T invP, typename F::T inv2P) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  shard_report<F, false>(p, gs, in, out, r, r, invP, inv2P);
+}
+
+// the one deferred launch of a call: the reports the fast launches marked, each lane walking the
+// reports of its column (report c, c + ld, ...: the chunks' reports that shared the column) one
+// after the other, so the marked reports of every chunk redo on the same scratch
+template <class F>
+__global__ __launch_bounds__(64) void k_shard_redo(DevParams p, GenScratch gs, ShardIn in,
+                                                   ShardOut out, typename F::T invP,
+                                                   typename F::T inv2P) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= p.ld) return;
+  for (uint64_t r = c; r < p.n; r += p.ld)
+    if (out.status[r] == SHARD_REDO) shard_report<F, true>(p, gs, in, out, (uint32_t)r, c, invP, inv2P);
 }
 
 // ====================================================================================
@@ -1369,6 +1522,25 @@ static int gen_mp64(prio3_engine* e, uint32_t n, uint64_t seed, uint64_t first_i
   return rc;
 }
 
+// The SoA scratch of k_gen and k_shard: slots[i] is the GenScratch member buffer i backs and
+// counts[i] its elements per report.  The first GEN_SHARD_BUFS are the client's shard (k_shard
+// takes only those); the rest belong to the generator's leader prepare_init.
+constexpr size_t GEN_SCRATCH_BUFS = 15, GEN_SHARD_BUFS = 11;
+static void gen_scratch_carve(const DevParams& p, GenScratch& gs, void** slots[GEN_SCRATCH_BUFS],
+                              size_t counts[GEN_SCRATCH_BUFS]) {
+  const size_t A = p.arity, P = p.P;
+  void** s[GEN_SCRATCH_BUFS] = {&gs.meas, &gs.hm, &gs.lm, &gs.wires, &gs.evals, &gs.g, &gs.tmp,
+                                &gs.proof, &gs.hp, &gs.prand, &gs.jr, &gs.qr, &gs.L, &gs.PV,
+                                &gs.acc};
+  const size_t c[GEN_SCRATCH_BUFS] = {p.meas_len, p.meas_len, p.meas_len, A * P, A * 2 * P, 2 * P,
+                                      2 * P, p.proof_len, p.proof_len, A,
+                                      p.jr_len ? p.jr_len : 1, 1, P, P, A};
+  for (size_t i = 0; i < GEN_SCRATCH_BUFS; i++) {
+    slots[i] = s[i];
+    counts[i] = c[i];
+  }
+}
+
 extern "C" int prio3_client_generate_device(prio3_engine* e, uint32_t n, uint64_t seed,
                                             uint64_t first_index, uint8_t* d_nonces,
                                             uint8_t* d_public_shares, uint8_t* d_helper_shares,
@@ -1402,12 +1574,10 @@ extern "C" int prio3_client_generate_device(prio3_engine* e, uint32_t n, uint64_
   std::vector<void*> bufs;
   int rc = PRIO3_OK;
   GenScratch gs;
-  void** slots[] = {&gs.meas, &gs.hm, &gs.lm, &gs.wires, &gs.evals, &gs.g, &gs.tmp, &gs.proof,
-                    &gs.hp, &gs.prand, &gs.jr, &gs.qr, &gs.L, &gs.PV, &gs.acc};
-  size_t counts[] = {p.meas_len, p.meas_len, p.meas_len, (size_t)A * P, (size_t)A * 2 * P,
-                     2 * (size_t)P, 2 * (size_t)P, p.proof_len, p.proof_len, A,
-                     p.jr_len ? p.jr_len : 1, 1, P, P, A};
-  for (size_t i = 0; i < sizeof(counts) / sizeof(counts[0]); i++) {
+  void** slots[GEN_SCRATCH_BUFS];
+  size_t counts[GEN_SCRATCH_BUFS];
+  gen_scratch_carve(p, gs, slots, counts);
+  for (size_t i = 0; i < GEN_SCRATCH_BUFS; i++) {
     void* b = nullptr;
     GCHK(hipMalloc(&b, counts[i] * chunk * es));
     bufs.push_back(b);
@@ -1447,5 +1617,277 @@ extern "C" int prio3_client_generate_device(prio3_engine* e, uint32_t n, uint64_
   GCHK(hipStreamSynchronize(st));
 done:
   for (auto b : bufs) (void)hipFree(b);
+  return rc;
+}
+
+// ====================================================================================
+// Client role (janus_prio3.h, "Client"): k_shard on pooled scratch, and the one call that chains
+// it with the two seals and the Report encode.
+// ====================================================================================
+static bool client_takes(const prio3_engine* e) { return e->dp.kind <= PRIO3_HISTOGRAM; }
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// bytes of k_shard's scratch per report column (every buffer a multiple of 512 bytes for ld % 64 == 0)
+static size_t shard_scratch_per_report(const DevParams& p) {
+  GenScratch gs;
+  void** slots[GEN_SCRATCH_BUFS];
+  size_t counts[GEN_SCRATCH_BUFS], per = 0;
+  gen_scratch_carve(p, gs, slots, counts);
+  for (size_t i = 0; i < GEN_SHARD_BUFS; i++) per += counts[i];
+  return per * p.es;
+}
+
+// k_shard over the m <= ld reports at `in` / `out` (ld % 64 == 0), or with redo the one deferred
+// k_shard_redo over all m reports (any m), on the scratch at base
+static int shard_launch(DevParams p, uint32_t m, uint32_t ld, uint8_t* base, const ShardIn& in,
+                        const ShardOut& out, bool redo, hipStream_t st) {
+  GenScratch gs{};
+  void** slots[GEN_SCRATCH_BUFS];
+  size_t counts[GEN_SCRATCH_BUFS];
+  gen_scratch_carve(p, gs, slots, counts);
+  for (size_t i = 0; i < GEN_SHARD_BUFS; i++) {
+    *slots[i] = base;
+    base += counts[i] * ld * p.es;
+  }
+  p.n = m;
+  p.ld = ld;
+  const uint32_t blocks = ((redo ? ld : m) + 63) / 64;
+  if (p.es == 16) {
+    const f128 ip = h128x(hpow(p.P, HP128 - 2, HP128)), i2 = h128x(hpow(2 * p.P, HP128 - 2, HP128));
+    if (redo)
+      k_shard_redo<Fp128><<<blocks, 64, 0, st>>>(p, gs, in, out, ip, i2);
+    else
+      k_shard<Fp128><<<blocks, 64, 0, st>>>(p, gs, in, out, ip, i2);
+  } else {
+    const uint64_t ip = (uint64_t)hpow(p.P, HP64 - 2, HP64), i2 = (uint64_t)hpow(2 * p.P, HP64 - 2, HP64);
+    if (redo)
+      k_shard_redo<Fp64><<<blocks, 64, 0, st>>>(p, gs, in, out, ip, i2);
+    else
+      k_shard<Fp64><<<blocks, 64, 0, st>>>(p, gs, in, out, ip, i2);
+  }
+  return hipGetLastError() == hipSuccess ? PRIO3_OK : PRIO3_EDEVICE;
+}
+
+// a slab of per * chunk bytes, the chunk halved (down to one wave) while the device cannot
+// provide it: all of the call's scratch or none of it
+static Slab* acquire_chunked(int device, size_t per, size_t& chunk, hipStream_t st, int* rc) {
+  for (;;) {
+    Slab* s = ws_acquire(device, per * chunk, st, rc);
+    if (s || chunk <= 64) return s;
+    chunk = std::max<size_t>(64, (chunk / 2) & ~(size_t)63);
+  }
+}
+
+extern "C" int prio3_client_rand_len(const prio3_params* params) {
+  prio3_sizes_t sz;
+  if (!params || prio3_sizes(params, &sz) != PRIO3_OK) return 0;
+  const uint32_t seed = sz.prep_msg_len ? sz.prep_msg_len : sz.helper_share_len / 2;
+  return (int)(seed * (sz.joint_rand_len ? 5 : 3));
+}
+
+extern "C" int prio3_client_shard_device(prio3_engine* e, uint32_t n,
+                                         const uint64_t* d_measurements, const uint8_t* d_nonces,
+                                         const uint8_t* d_rand, uint8_t* d_public_shares,
+                                         uint8_t* d_leader_input_shares, uint8_t* d_helper_shares,
+                                         uint8_t* d_status, void* stream) {
+  if (!e) return PRIO3_EINVAL;
+  if (!client_takes(e)) return PRIO3_EUNSUPPORTED;
+  if (n == 0) return PRIO3_OK;
+  if (!d_measurements || !d_nonces || !d_rand || !d_leader_input_shares || !d_helper_shares ||
+      !d_status || (e->dp.public_share_len && !d_public_shares))
+    return PRIO3_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  DeviceGuard dg_(e->device);
+  if (dg_.rc != hipSuccess) return PRIO3_EDEVICE;
+  hipStream_t st = (hipStream_t)stream;
+  DevParams p = e->dp;
+  p.force_slow = (uint32_t)e->force_slow;
+  const size_t per = shard_scratch_per_report(p);
+  size_t chunk = std::min<size_t>({((size_t)n + 63) & ~(size_t)63, (size_t)65536,
+                                   std::max<size_t>(64, (((size_t)2 << 30) / per) & ~(size_t)63)});
+  int rc = PRIO3_OK;
+  Slab* slab = acquire_chunked(e->device, per, chunk, st, &rc);
+  if (!slab) return rc;
+  const uint32_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1;
+  const uint32_t rl = p.jr_len ? 80 : 48;
+  for (uint64_t off = 0; off < n && rc == PRIO3_OK; off += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
+    ShardIn in{d_measurements + (size_t)mstride * off, d_nonces + 16 * off, d_rand + (size_t)rl * off};
+    ShardOut out{d_public_shares ? d_public_shares + (size_t)p.public_share_len * off : nullptr,
+                 d_leader_input_shares + (size_t)p.leader_share_len * off,
+                 d_helper_shares + (size_t)p.helper_share_len * off, d_status + off};
+    rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, false, st);
+  }
+  if (rc == PRIO3_OK) {  // the reports that met a rejection, all chunks' in one launch
+    ShardIn in{d_measurements, d_nonces, d_rand};
+    ShardOut out{d_public_shares, d_leader_input_shares, d_helper_shares, d_status};
+    rc = shard_launch(p, n, (uint32_t)chunk, slab->base, in, out, true, st);
+  }
+  ws_release(slab, st);
+  return rc;
+}
+
+extern "C" int prio3_client_shard_batch(prio3_engine* e, uint32_t n, const uint64_t* measurements,
+                                        const uint8_t* nonces, const uint8_t* rand,
+                                        uint8_t* public_shares, uint8_t* leader_input_shares,
+                                        uint8_t* helper_shares, uint8_t* status) {
+  if (!e) return PRIO3_EINVAL;
+  if (!client_takes(e)) return PRIO3_EUNSUPPORTED;
+  if (n == 0) return PRIO3_OK;
+  const DevParams& p = e->dp;
+  if (!measurements || !nonces || !rand || !leader_input_shares || !helper_shares || !status ||
+      (p.public_share_len && !public_shares))
+    return PRIO3_EINVAL;
+  DeviceGuard dg_(e->device);
+  if (dg_.rc != hipSuccess) return PRIO3_EDEVICE;
+  hipStream_t st = ws_stream_get(e->device);
+  if (!st) return PRIO3_EDEVICE;
+  const size_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1, rl = p.jr_len ? 80 : 48;
+  const size_t sizes[7] = {8 * mstride * n, 16 * (size_t)n, rl * n, (size_t)p.public_share_len * n,
+                           (size_t)p.leader_share_len * n, (size_t)p.helper_share_len * n, n};
+  size_t offs[8] = {0};
+  for (int i = 0; i < 7; i++) offs[i + 1] = offs[i] + up256(sizes[i]);
+  int rc = PRIO3_OK;
+  Slab* slab = ws_acquire(e->device, offs[7], st, &rc);
+  if (slab) {
+    uint8_t* b = slab->base;
+    const void* src[3] = {measurements, nonces, rand};
+    uint8_t* dst[4] = {public_shares, leader_input_shares, helper_shares, status};
+    for (int i = 0; i < 3 && rc == PRIO3_OK; i++)
+      if (hipMemcpyAsync(b + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = PRIO3_EDEVICE;
+    if (rc == PRIO3_OK)
+      rc = prio3_client_shard_device(e, n, (const uint64_t*)(b + offs[0]), b + offs[1], b + offs[2],
+                                     b + offs[3], b + offs[4], b + offs[5], b + offs[6], st);
+    for (int i = 0; i < 4 && rc == PRIO3_OK; i++)
+      if (sizes[3 + i] &&
+          hipMemcpyAsync(dst[i], b + offs[3 + i], sizes[3 + i], hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = PRIO3_EDEVICE;
+    if (hipStreamSynchronize(st) != hipSuccess && rc == PRIO3_OK) rc = PRIO3_EDEVICE;
+    ws_release(slab, st);
+  }
+  ws_stream_put(e->device, st);
+  return rc;
+}
+
+// times rounded down to the task's time precision (to_batch_interval_start)
+__global__ void k_client_round_times(const uint64_t* t, uint64_t prec, uint64_t* out, uint32_t n) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) out[r] = t[r] - t[r] % prec;
+}
+// status per report: the shard's, then the leader seal's, then the helper seal's
+__global__ void k_client_status(const uint8_t* shard, const uint8_t* ls, const uint8_t* hs,
+                                uint8_t* out, uint32_t n) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) out[r] = shard[r] ? shard[r] : (ls[r] ? ls[r] : hs[r]);
+}
+
+static uint32_t sealed_stride(uint32_t share_len, int taskprov) {
+  return (uint32_t)(((taskprov ? 10u : 6u) + (size_t)share_len + 16 + 15) & ~(size_t)15);
+}
+
+extern "C" int prio3_client_report_stride(const prio3_params* params, const janus_hpke_sealer* ls,
+                                          const janus_hpke_sealer* hs, int taskprov) {
+  prio3_sizes_t sz;
+  if (!params || !ls || !hs || prio3_sizes(params, &sz) != PRIO3_OK) return 0;
+  const size_t len = janus_dap_report_max_len(
+      sz.public_share_len, (uint32_t)hpke_sealer_nenc(ls),
+      sealed_stride(sz.leader_input_share_len, taskprov), (uint32_t)hpke_sealer_nenc(hs),
+      sealed_stride(sz.helper_share_len, taskprov));
+  return len < ((size_t)1 << 31) ? (int)len : 0;
+}
+
+extern "C" int prio3_client_prepare_reports_device(
+    prio3_engine* e, janus_hpke_sealer* lsl, janus_hpke_sealer* hsl, uint32_t n,
+    const uint8_t task_id[32], uint64_t time_precision, const uint64_t* d_measurements,
+    const uint8_t* d_report_ids, const uint64_t* d_times, const uint8_t* d_rand,
+    const uint8_t* d_sk_e_leader, const uint8_t* d_sk_e_helper, uint8_t leader_config_id,
+    uint8_t helper_config_id, int taskprov, uint8_t* d_reports, uint32_t report_stride,
+    uint32_t* d_report_len, uint8_t* d_status, void* stream) {
+  if (!e) return PRIO3_EINVAL;
+  if (!client_takes(e)) return PRIO3_EUNSUPPORTED;
+  if (!lsl || !hsl || !task_id || time_precision == 0 || hpke_sealer_device(lsl) != e->device ||
+      hpke_sealer_device(hsl) != e->device)
+    return PRIO3_EINVAL;
+  const uint32_t lenc = (uint32_t)hpke_sealer_nenc(lsl), henc = (uint32_t)hpke_sealer_nenc(hsl);
+  if ((lenc != 32 && lenc != 65) || (henc != 32 && henc != 65)) return PRIO3_EINVAL;
+  const int need = prio3_client_report_stride(&e->params, lsl, hsl, taskprov);
+  if (need <= 0 || report_stride < (uint32_t)need) return PRIO3_EINVAL;
+  if (n == 0) return PRIO3_OK;
+  if (!d_measurements || !d_report_ids || !d_times || !d_rand || !d_sk_e_leader || !d_sk_e_helper ||
+      !d_reports || !d_report_len || !d_status)
+    return PRIO3_EINVAL;
+  DeviceGuard dg_(e->device);
+  if (dg_.rc != hipSuccess) return PRIO3_EDEVICE;
+  hipStream_t st = (hipStream_t)stream;
+  DevParams p;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    p = e->dp;
+    p.force_slow = (uint32_t)e->force_slow;
+  }
+  const uint32_t psl = p.public_share_len, L = p.leader_share_len, H = p.helper_share_len;
+  const uint32_t lcs = sealed_stride(L, taskprov), hcs = sealed_stride(H, taskprov);
+  // per-report scratch: the shard's SoA columns, the three share rows, both ciphertexts with their
+  // enc, length and status, the shard status and the rounded time (each array 256-byte aligned:
+  // 16 arrays' slack below)
+  const size_t rows[13] = {psl, L, H, lenc, lcs, 4, 1, henc, hcs, 4, 1, 1, 8};
+  const size_t shard_per = shard_scratch_per_report(p);
+  size_t per = shard_per;
+  for (size_t b : rows) per += b;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) return PRIO3_EDEVICE;
+  size_t chunk = std::min<size_t>({((size_t)n + 63) & ~(size_t)63, (size_t)65536,
+                                   std::max<size_t>(64, ((size_t)(0.4 * (double)fr) / per) & ~(size_t)63)});
+  int rc = PRIO3_OK;
+  Slab* slab = acquire_chunked(e->device, per + 64, chunk, st, &rc);  // 64 B/report >= 16 x 256 / 64
+  if (!slab) return rc;
+  uint8_t* arr[13];
+  {
+    uint8_t* b = slab->base + up256(shard_per * chunk);
+    for (int i = 0; i < 13; i++) {
+      arr[i] = b;
+      b += up256(rows[i] * chunk);
+    }
+  }
+  uint8_t *a_pub = arr[0], *a_lin = arr[1], *a_hsh = arr[2], *a_lenc = arr[3], *a_lct = arr[4],
+          *a_lst = arr[6], *a_henc = arr[7], *a_hct = arr[8], *a_hst = arr[10], *a_sst = arr[11];
+  uint32_t *a_lcl = (uint32_t*)arr[5], *a_hcl = (uint32_t*)arr[9];
+  uint64_t* a_t = (uint64_t*)arr[12];
+  const uint32_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1;
+  const uint32_t rl = p.jr_len ? 80 : 48;
+  for (uint64_t off = 0; off < n && rc == PRIO3_OK; off += chunk) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
+    const uint8_t* ids = d_report_ids + 16 * off;
+    k_client_round_times<<<(m + 255) / 256, 256, 0, st>>>(d_times + off, time_precision, a_t, m);
+    ShardIn in{d_measurements + (size_t)mstride * off, ids, d_rand + (size_t)rl * off};
+    ShardOut out{a_pub, a_lin, a_hsh, a_sst};
+    rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, false, st);
+    if (rc == PRIO3_OK) rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, true, st);
+    if (rc != PRIO3_OK) break;
+    int hrc = janus_hpke_seal_input_shares_device(lsl, m, task_id, d_sk_e_leader + 32 * off, ids,
+                                                  a_t, psl ? a_pub : nullptr, psl, a_lin, L,
+                                                  taskprov, a_lenc, a_lct, a_lcl, lcs, a_lst, st);
+    if (hrc == JANUS_HPKE_SUCCESS)
+      hrc = janus_hpke_seal_input_shares_device(hsl, m, task_id, d_sk_e_helper + 32 * off, ids, a_t,
+                                                psl ? a_pub : nullptr, psl, a_hsh, H, taskprov,
+                                                a_henc, a_hct, a_hcl, hcs, a_hst, st);
+    if (hrc != JANUS_HPKE_SUCCESS) {
+      rc = hrc;  // the two headers share their whole-call codes
+      break;
+    }
+    k_client_status<<<(m + 255) / 256, 256, 0, st>>>(a_sst, a_lst, a_hst, d_status + off, m);
+    if (hipGetLastError() != hipSuccess) {
+      rc = PRIO3_EDEVICE;
+      break;
+    }
+    const int drc = janus_dap_report_encode_device(
+        m, ids, a_t, psl ? a_pub : nullptr, psl, leader_config_id, a_lenc, lenc, a_lct, a_lcl, lcs,
+        helper_config_id, a_henc, henc, a_hct, a_hcl, hcs, d_status + off,
+        d_reports + (size_t)report_stride * off, report_stride, d_report_len + off, st);
+    if (drc != 0) rc = drc == JANUS_DAP_EDEVICE ? PRIO3_EDEVICE : PRIO3_EINVAL;
+  }
+  ws_release(slab, st);
   return rc;
 }

@@ -408,4 +408,8 @@ void hpke_layout(const HpkeJob* j, uint32_t cap, HpkeLayout* L);
 int hpke_group_issue(const HpkeJob& proto, const HpkeLayout& L, const uint8_t* stg, uint8_t* out,
                      uint32_t n, hipStream_t* st_out, Slab** slab_out, bool own_queue);
 int exec_hpke(HpkeJob* job);
+// the sealer's GPU and its KEM's Nenc (prio3_client_prepare_reports_device)
+struct janus_hpke_sealer;
+int hpke_sealer_device(const janus_hpke_sealer* s);
+size_t hpke_sealer_nenc(const janus_hpke_sealer* s);
 

@@ -19,6 +19,8 @@ DAP_EXPORTED_SYMBOLS = (
     "janus_dap_agg_init_req_max_len", "janus_dap_agg_init_req_encode_host",
     "janus_dap_agg_init_req_encode_device", "janus_dap_agg_job_resp_unpack_host",
     "janus_dap_agg_job_resp_unpack_device",
+    # client side
+    "janus_dap_report_max_len", "janus_dap_report_encode_device", "janus_dap_report_encode_host",
 )
 NO_ERROR = 0xFF  # prepare_error value meaning "no DAP-level error for this report"
 
@@ -64,6 +66,13 @@ def _lib():
                                                          vp]
         L.janus_dap_agg_job_resp_unpack_device.argtypes = [u32, vp, vp, u32, vp, C.c_size_t, u32,
                                                            vp, vp, vp, vp, vp]
+        rep = [u32, vp, vp, vp, u32, u8, vp, u32, vp, vp, u32, u8, vp, u32, vp, vp, u32, vp, vp,
+               u32, vp]
+        L.janus_dap_report_max_len.argtypes = [u32] * 5
+        L.janus_dap_report_max_len.restype = C.c_size_t
+        L.janus_dap_report_encode_host.argtypes = rep
+        L.janus_dap_report_encode_host.restype = C.c_int64
+        L.janus_dap_report_encode_device.argtypes = rep + [vp]
         _bound = True
     return L
 
@@ -404,3 +413,103 @@ def unpack_resp_device(d_body, body_len: int, index, report_ids, n_included: int
     if rc:
         raise RuntimeError(f"janus_dap_agg_job_resp_unpack_device failed (rc={rc})")
     return msgs, pe, flags
+
+
+# ---- client side: the upload body ---------------------------------------------------------
+def report_max_len(public_share_len: int, leader_enc_len: int, leader_ct_stride: int,
+                   helper_enc_len: int, helper_ct_stride: int) -> int:
+    """Row length that holds any Report of these field lengths (janus_dap_report_max_len)."""
+    return _lib().janus_dap_report_max_len(public_share_len, leader_enc_len, leader_ct_stride,
+                                           helper_enc_len, helper_ct_stride)
+
+
+def _report_shapes(n, public_shares, cts, out_stride):
+    """Argument rules shared by both Report encoders; returns (public share length, stride)."""
+    psl = 0 if public_shares is None else public_shares.shape[1]
+    if public_shares is not None and (len(public_shares.shape) != 2 or public_shares.shape[0] != n):
+        raise ValueError("public_shares must be None or [n, public_share_len]")
+    for who, (cfg, enc, ct, ct_len) in cts.items():
+        if not 0 <= int(cfg) <= 0xFF:
+            raise ValueError(f"{who}_config_id is one byte")
+        if len(enc.shape) != 2 or enc.shape[0] != n or enc.shape[1] > 0xFFFF:
+            raise ValueError(f"{who}_enc must be [n, enc_len] with a u16-prefixed enc_len")
+        if len(ct.shape) != 2 or ct.shape[0] != n or tuple(ct_len.shape) != (n,):
+            raise ValueError(f"{who}_ct must be [n, ct_stride] and {who}_ct_len [n]")
+    need = report_max_len(psl, cts["leader"][1].shape[1], cts["leader"][2].shape[1],
+                          cts["helper"][1].shape[1], cts["helper"][2].shape[1])
+    stride = need if out_stride is None else int(out_stride)
+    if stride < need:
+        raise ValueError(f"out_stride must be >= report_max_len(...) = {need}")
+    return psl, stride
+
+
+def report_encode_host(report_ids, times, public_shares, leader_config_id: int, leader_enc,
+                       leader_ct, leader_ct_len, helper_config_id: int, helper_enc, helper_ct,
+                       helper_ct_len, skip=None, out_stride=None):
+    """DAP ``Report`` rows from host SoA buffers: returns (out uint8 [n, out_stride], out_len
+    uint32 [n]).  A report whose skip byte is non-zero, or one of whose ct_len is 0 or above its
+    row, is left out (length 0, zero row)."""
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    ids, tm = c(report_ids, np.uint8), c(times, np.uint64)
+    n = ids.shape[0]
+    if ids.shape != (n, 16) or tm.shape != (n,):
+        raise ValueError("report_ids must be [n, 16] and times [n]")
+    pub = None if public_shares is None or np.shape(public_shares)[1] == 0 else \
+        c(public_shares, np.uint8)
+    le, lc, ll = c(leader_enc, np.uint8), c(leader_ct, np.uint8), c(leader_ct_len, np.uint32)
+    he, hc, hl = c(helper_enc, np.uint8), c(helper_ct, np.uint8), c(helper_ct_len, np.uint32)
+    sk = None if skip is None else c(skip, np.uint8)
+    if sk is not None and sk.shape != (n,):
+        raise ValueError("skip must be [n]")
+    psl, stride = _report_shapes(n, pub, dict(leader=(leader_config_id, le, lc, ll),
+                                              helper=(helper_config_id, he, hc, hl)), out_stride)
+    out = np.zeros((n, stride), np.uint8)
+    out_len = np.zeros(n, np.uint32)
+    w = lambda a: _np_ptr(a) if a is not None and a.size else None  # noqa: E731
+    rc = _lib().janus_dap_report_encode_host(
+        n, _np_ptr(ids), _np_ptr(tm), w(pub), psl, leader_config_id, w(le), le.shape[1], w(lc),
+        _np_ptr(ll), lc.shape[1], helper_config_id, w(he), he.shape[1], w(hc), _np_ptr(hl),
+        hc.shape[1], _np_ptr(sk), _np_ptr(out), stride, _np_ptr(out_len))
+    if rc < 0:
+        raise ValueError(f"janus_dap_report_encode_host failed (rc={rc})")
+    return out, out_len
+
+
+def report_encode_device(report_ids, times, public_shares, leader_config_id: int, leader_enc,
+                         leader_ct, leader_ct_len, helper_config_id: int, helper_enc, helper_ct,
+                         helper_ct_len, skip=None, out_stride=None, stream=None):
+    """Device form on torch tensors of one GPU (times 8-byte, ct_len 4-byte integers, the rows as
+    HpkeSealer.seal_input_shares_device writes them).  Returns (out uint8 [n, out_stride],
+    out_len int32 [n]); no host synchronisation."""
+    import torch
+    dev = report_ids.device
+    if dev.type != "cuda":
+        raise ValueError("report_encode_device takes GPU tensors")
+    n = report_ids.shape[0]
+    if tuple(report_ids.shape) != (n, 16) or tuple(times.shape) != (n,):
+        raise ValueError("report_ids must be [n, 16] and times [n]")
+    pub = None if public_shares is None or public_shares.shape[1] == 0 else public_shares
+    psl, stride = _report_shapes(n, pub, dict(
+        leader=(leader_config_id, leader_enc, leader_ct, leader_ct_len),
+        helper=(helper_config_id, helper_enc, helper_ct, helper_ct_len)), out_stride)
+    for k, v, es in (("report_ids", report_ids, 1), ("times", times, 8), ("public_shares", pub, 1),
+                     ("leader_enc", leader_enc, 1), ("leader_ct", leader_ct, 1),
+                     ("leader_ct_len", leader_ct_len, 4), ("helper_enc", helper_enc, 1),
+                     ("helper_ct", helper_ct, 1), ("helper_ct_len", helper_ct_len, 4),
+                     ("skip", skip, 1)):
+        if v is not None:
+            _dev_tensor(k, v, es, dev)
+    if skip is not None and tuple(skip.shape) != (n,):
+        raise ValueError("skip must be [n]")
+    out = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    w = lambda t: _tptr(t) if t is not None and t.numel() else None  # noqa: E731
+    rc = _lib().janus_dap_report_encode_device(
+        n, _tptr(report_ids), _tptr(times), w(pub), psl, leader_config_id, w(leader_enc),
+        leader_enc.shape[1], w(leader_ct), _tptr(leader_ct_len), leader_ct.shape[1],
+        helper_config_id, w(helper_enc), helper_enc.shape[1], w(helper_ct), _tptr(helper_ct_len),
+        helper_ct.shape[1], _tptr(skip), _tptr(out), stride, _tptr(out_len),
+        _stream(stream, dev.index or 0))
+    if rc:
+        raise RuntimeError(f"janus_dap_report_encode_device failed (rc={rc})")
+    return out, out_len

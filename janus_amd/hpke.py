@@ -34,6 +34,7 @@ OK, DECRYPT_ERROR, INVALID_MESSAGE = 0, 4, 8
 SEAL_KEY_ERROR, SEAL_LENGTH_ERROR = 0x40, 0x41
 NSK_E = 32  # bytes of ephemeral private key per report (both seal KEMs)
 INFO_INPUT_SHARE_HELPER = b"dap-09 input share" + bytes([1, 3])  # Label::InputShare, Client->Helper
+INFO_INPUT_SHARE_LEADER = b"dap-09 input share" + bytes([1, 2])  # Label::InputShare, Client->Leader
 
 _bound = False
 

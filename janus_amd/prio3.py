@@ -108,6 +108,8 @@ EXPORTED_SYMBOLS = (
     "prio3_executor_stats_get", "prio3_helper_aggregate_init_batch",
     "prio3_helper_aggregate_init_batch_ex",
     "prio3_leader_prepare_next_aggregate_batch",
+    "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
+    "prio3_client_rand_len", "prio3_client_report_stride",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -195,6 +197,13 @@ def load_library() -> C.CDLL:
                                               vp, vp]
     L.prio3_batch_metadata.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.prio3_device_combine_metadata.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.prio3_client_rand_len.argtypes = [P(Prio3Params)]
+    L.prio3_client_shard_device.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.prio3_client_shard_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.prio3_client_report_stride.argtypes = [P(Prio3Params), vp, vp, C.c_int]
+    L.prio3_client_prepare_reports_device.argtypes = [vp, vp, vp, u32, vp, C.c_uint64, vp, vp, vp,
+                                                      vp, vp, vp, C.c_uint8, C.c_uint8, C.c_int,
+                                                      vp, u32, vp, vp, vp]
     _lib = L
     return L
 
@@ -788,6 +797,130 @@ class HelperEngine:
             out["public_shares"] if self.sz.public_share_len else None, out["helper_shares"],
             out["enc"], out["ct"], out["ct_len"], out["seal_status"],
             with_taskprov_extension=with_taskprov_extension, stream=stream)
+        return out
+
+    # ---- client role -------------------------------------------------------------------
+    @property
+    def rand_len(self) -> int:
+        """Bytes of shard randomness per report (prio3_client_rand_len)."""
+        return load_library().prio3_client_rand_len(C.byref(self.vdaf.params()))
+
+    def _client_shapes(self, n, measurements, nonces, rand):
+        if self.vdaf.kind not in (PRIO3_COUNT, PRIO3_SUM, PRIO3_SUMVEC, PRIO3_HISTOGRAM):
+            raise NotImplementedError("the client role takes Count, Sum, SumVec and Histogram")
+        mstride = self.vdaf.length if self.vdaf.kind == PRIO3_SUMVEC else 1
+        if tuple(measurements.shape) not in ((n, mstride),) + (((n,),) if mstride == 1 else ()):
+            raise ValueError(f"measurements must be [{n}, {mstride}]")
+        if tuple(nonces.shape) != (n, 16):
+            raise ValueError(f"nonces (the report IDs) must be [{n}, 16]")
+        if tuple(rand.shape) != (n, self.rand_len):
+            raise ValueError(f"rand must be [{n}, {self.rand_len}]")
+
+    def shard_device(self, measurements, nonces, rand, stream=None) -> dict:
+        """prio ``Prio3::shard`` of the caller's measurements on the GPU (prio3_client_shard_device).
+
+        torch tensors on this engine's device: measurements [n, length] (SumVec) or [n] / [n, 1],
+        8-byte integers; nonces [n, 16] uint8 (the report IDs); rand [n, rand_len] uint8 from the
+        caller's CSPRNG (layout: janus_prio3.h).  Returns public_shares, leader_input_shares,
+        helper_shares (uint8 rows) and status [n] (1 = invalid measurement, rows zero).
+        Stream-ordered, no host synchronisation."""
+        import torch
+        n = nonces.shape[0] if len(nonces.shape) else -1
+        self._client_shapes(n, measurements, nonces, rand)
+        if measurements.element_size() != 8:
+            raise ValueError("measurements must be 8-byte integers")
+        for t in (measurements, nonces, rand):
+            if not isinstance(t, torch.Tensor) or not t.is_contiguous() or \
+                    t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("tensors must be contiguous and on the engine's GPU")
+        sz = self.sz
+        u8 = dict(dtype=torch.uint8, device=torch.device("cuda", self.device))
+        out = dict(public_shares=torch.empty((n, sz.public_share_len), **u8),
+                   leader_input_shares=torch.empty((n, sz.leader_input_share_len), **u8),
+                   helper_shares=torch.empty((n, sz.helper_share_len), **u8),
+                   status=torch.empty(n, **u8))
+        rc = load_library().prio3_client_shard_device(
+            self.handle, n, _tptr(measurements), _tptr(nonces), _tptr(rand),
+            _tptr(out["public_shares"]) if sz.public_share_len else None,
+            _tptr(out["leader_input_shares"]), _tptr(out["helper_shares"]), _tptr(out["status"]),
+            _stream(stream, self.device))
+        if rc:
+            raise RuntimeError(f"prio3_client_shard_device failed (rc={rc})")
+        return out
+
+    def shard_batch(self, measurements, nonces, rand) -> dict:
+        """The numpy form of ``shard_device`` (prio3_client_shard_batch, blocking)."""
+        m = np.ascontiguousarray(measurements, np.uint64)
+        ids = np.ascontiguousarray(nonces, np.uint8)
+        rnd = np.ascontiguousarray(rand, np.uint8)
+        n = ids.shape[0] if ids.ndim else -1
+        self._client_shapes(n, m, ids, rnd)
+        sz = self.sz
+        out = dict(public_shares=np.zeros((n, sz.public_share_len), np.uint8),
+                   leader_input_shares=np.zeros((n, sz.leader_input_share_len), np.uint8),
+                   helper_shares=np.zeros((n, sz.helper_share_len), np.uint8),
+                   status=np.zeros(n, np.uint8))
+        rc = load_library().prio3_client_shard_batch(
+            self.handle, n, _np_ptr(m), _np_ptr(ids), _np_ptr(rnd),
+            _np_ptr(out["public_shares"]) if sz.public_share_len else None,
+            _np_ptr(out["leader_input_shares"]), _np_ptr(out["helper_shares"]),
+            _np_ptr(out["status"]))
+        if rc:
+            raise RuntimeError(f"prio3_client_shard_batch failed (rc={rc})")
+        return out
+
+    def prepare_reports_device(self, leader_sealer, helper_sealer, task_id: bytes,
+                               time_precision: int, measurements, report_ids, times, rand,
+                               sk_e_leader, sk_e_helper, leader_config_id: int,
+                               helper_config_id: int, with_taskprov_extension: bool = False,
+                               report_stride=None, stream=None) -> dict:
+        """``Client::prepare_report`` for a batch of one task in one call
+        (prio3_client_prepare_reports_device): times rounded down to ``time_precision``, the shard,
+        one input share sealed to each aggregator (janus_amd.hpke.HpkeSealer objects on this
+        engine's GPU; sk_e_leader / sk_e_helper [n, 32] uint8, one fresh ephemeral key per report
+        and aggregator) and the DAP ``Report`` encode.  torch tensors on the GPU; times are 8-byte
+        integers.  Returns reports [n, stride] (uint8), report_len [n] (int32; 0 = left out) and
+        status [n] (0, 1 = invalid measurement, 0x40 / 0x41 = the sealer's)."""
+        import torch
+        from .hpke import NSK_E
+        n = report_ids.shape[0] if len(report_ids.shape) else -1
+        if len(task_id) != 32:
+            raise ValueError("task_id must be 32 bytes")
+        if int(time_precision) <= 0:
+            raise ValueError("time_precision must be positive")
+        if leader_sealer.device != self.device or helper_sealer.device != self.device:
+            raise ValueError("a sealer is bound to another GPU than the engine")
+        if not 0 <= leader_config_id <= 0xFF or not 0 <= helper_config_id <= 0xFF:
+            raise ValueError("an HPKE config id is one byte")
+        self._client_shapes(n, measurements, report_ids, rand)
+        if tuple(times.shape) != (n,) or tuple(sk_e_leader.shape) != (n, NSK_E) or \
+                tuple(sk_e_helper.shape) != (n, NSK_E):
+            raise ValueError(f"times must be [{n}], sk_e_leader and sk_e_helper [{n}, {NSK_E}]")
+        if times.element_size() != 8 or measurements.element_size() != 8:
+            raise ValueError("times and measurements must be 8-byte integers")
+        for t in (measurements, report_ids, times, rand, sk_e_leader, sk_e_helper):
+            if not isinstance(t, torch.Tensor) or not t.is_contiguous() or \
+                    t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("tensors must be contiguous and on the engine's GPU")
+        L = load_library()
+        need = L.prio3_client_report_stride(C.byref(self.vdaf.params()), leader_sealer.handle,
+                                            helper_sealer.handle, int(bool(with_taskprov_extension)))
+        stride = need if report_stride is None else int(report_stride)
+        if need == 0 or stride < need:
+            raise ValueError(f"report_stride must be >= {need}")
+        dev = torch.device("cuda", self.device)
+        out = dict(reports=torch.empty((n, stride), dtype=torch.uint8, device=dev),
+                   report_len=torch.empty(n, dtype=torch.int32, device=dev),
+                   status=torch.empty(n, dtype=torch.uint8, device=dev))
+        tid = (C.c_uint8 * 32).from_buffer_copy(bytes(task_id))
+        rc = L.prio3_client_prepare_reports_device(
+            self.handle, leader_sealer.handle, helper_sealer.handle, n, tid, int(time_precision),
+            _tptr(measurements), _tptr(report_ids), _tptr(times), _tptr(rand), _tptr(sk_e_leader),
+            _tptr(sk_e_helper), leader_config_id, helper_config_id,
+            int(bool(with_taskprov_extension)), _tptr(out["reports"]), stride,
+            _tptr(out["report_len"]), _tptr(out["status"]), _stream(stream, self.device))
+        if rc:
+            raise RuntimeError(f"prio3_client_prepare_reports_device failed (rc={rc})")
         return out
 
     # ---- measurement ----------------------------------------------------------------
