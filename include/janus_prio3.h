@@ -481,6 +481,12 @@ int prio3_trace_enabled(void);
  * Lets tests pin the hand-written asm arithmetic against Python integers directly. */
 int prio3_selftest_field(int op, uint32_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 
+/* Test-only: runs the fused accumulate's tile reduction on one wave's host-supplied values.
+ * values: [8][64][16 B], slot-major (slot s of lane l at (s * 64 + l) * 16, LE Field128 words);
+ * all 8 slots are staged, the first n_elems (1..8) are reduced.  out: [n_elems][8] uint32, the 8
+ * addends of each slot's sum over the 64 lanes, addend h at weight 2^(16 h), each < 2^22. */
+int prio3_selftest_tile(uint32_t n_elems, const uint8_t* values, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,11 @@
 #include "sha256_device.h"
 #include "sha256_host.h"
 
+// threads per block of the kernels with the fused accumulate (k_prep_h, k_xofd): each of their
+// waves owns 8 KiB of the block's LDS (xofd_body), 32 KiB per block and 96 KiB per CU
+#ifndef XOFD_BLOCK
+#define XOFD_BLOCK 256
+#endif
 #ifndef XOFD_OCC
 #define XOFD_OCC 3
 #endif
@@ -298,41 +303,78 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
   uint32_t pend0 = 0, pend1 = 0;
   TruncSink ts(p, sc.out, r);
   const int Mi = (int)M;
-  // wave totals of share elements e0, e0+1 (zero outside [0, M)), slot lane of lanes 0..15
-  auto fused_pair = [&](int e0, f128 a, f128 b2) __attribute__((always_inline)) {
-    if (e0 >= Mi) return;  // wave-uniform
-    if (haspad && oor) {   // wave-uniform test; the masked lanes add nothing
-      a = zero128();
-      b2 = zero128();
-    }
-    const uint32_t tot = wave_halfsum2(a, b2, lane);  // slot lane >> 2 on each lane of a quad
-    const int e = e0 + (int)(lane >> 5);
-    if ((lane & 3u) == 0 && e < Mi)
-      sc.wpart[((size_t)(r >> 6) * M + (uint32_t)e) * 8u + ((lane >> 2) & 7u)] = tot;
+  // The fused accumulate: the wave totals of the share elements go to sc.wpart a tile at a time
+  // through the wave's 8 KiB of LDS (tile_stage / tile_halfsum, prio3_device.h).  Two share
+  // blocks hold 21 elements, e0 .. e0+20 with e0 = 21 (b >> 1): 10 whole ones and the first half
+  // of e0+10 in the even block, the rest in the odd one.  They are cut into the tiles
+  // A = e0..e0+7, B = e0+8..e0+15 and C = e0+16..e0+20, staged and flushed at two places per
+  // block, fuse_top before and fuse_mid after the joint-rand permutation, so that every flush
+  // reads what was stored a permutation earlier and all 8 slots are free again when it has run:
+  //   even top: flush C of the blocks before, stage A     even mid: flush A, stage e0+8, e0+9
+  //   odd top:  stage e0+10 .. e0+15                      odd mid:  flush B, stage C
+  // and fuse_tail after the last block's fuse_mid flushes what that has staged.  Elements >= M
+  // are neither staged nor stored.
+  uint4* tile = nullptr;
+  if constexpr (FUSE) {
+    __shared__ uint4 fuse_tiles[XOFD_BLOCK / 64][FTILE * 64];
+    tile = fuse_tiles[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+  }
+  // the wave's rows of sc.wpart: a scalar base (r >> 6 is the same on all 64 lanes), except in
+  // the pulling variant, which has no two SGPRs left for it through the share loop (it spilled
+  // them and grew its frame to 80 B) and forms the address per lane instead
+  uint32_t* const wrow =
+      FUSE && !PULL ? sc.wpart + (size_t)__builtin_amdgcn_readfirstlane(r >> 6) * M * 8u
+                    : nullptr;
+  const uint32_t wlane = (lane & 7u) * 8u + (lane >> 3);
+  auto mword = [&](int w) __attribute__((always_inline)) {  // the element at words w .. w+3 of ms
+    return mk128(kword(ms, w), kword(ms, w + 1), kword(ms, w + 2), kword(ms, w + 3));
   };
-  // the elements squeezed from share block b (state ms, pend = carried half element)
-  auto fuse_block = [&](uint32_t b, uint32_t q0, uint32_t q1) __attribute__((always_inline)) {
-    const int e0 = 21 * (int)(b >> 1);
-    const f128 z = zero128();
-    if ((b & 1) == 0) {
-#pragma unroll
-      for (int t = 0; t < 10; t += 2)
-        fused_pair(e0 + t, mk128(kword(ms, 4 * t), kword(ms, 4 * t + 1), kword(ms, 4 * t + 2),
-                                 kword(ms, 4 * t + 3)),
-                   mk128(kword(ms, 4 * t + 4), kword(ms, 4 * t + 5), kword(ms, 4 * t + 6),
-                         kword(ms, 4 * t + 7)));
-    } else {
-      fused_pair(e0 + 10, mk128(q0, q1, kword(ms, 0), kword(ms, 1)),
-                 mk128(kword(ms, 2), kword(ms, 3), kword(ms, 4), kword(ms, 5)));
-#pragma unroll
-      for (int t = 1; t < 10; t += 2)
-        fused_pair(e0 + 11 + t,
-                   mk128(kword(ms, 2 + 4 * t), kword(ms, 3 + 4 * t), kword(ms, 4 + 4 * t),
-                         kword(ms, 5 + 4 * t)),
-                   t + 1 < 10 ? mk128(kword(ms, 6 + 4 * t), kword(ms, 7 + 4 * t),
-                                      kword(ms, 8 + 4 * t), kword(ms, 9 + 4 * t))
-                              : z);
+  auto stage = [&](int e, int slot, f128 x) __attribute__((always_inline)) {
+    if (e >= Mi) return;               // wave-uniform
+    if (haspad && oor) x = zero128();  // wave-uniform test; the masked lanes add nothing
+    tile_stage(tile, slot, lane, x);
+  };
+  // slots 0 .. n-1 hold elements eb .. eb+n-1; lane l stores element eb + (l & 7), addend l >> 3
+  auto flush = [&](int eb, int n) __attribute__((always_inline)) {
+    const int cnt = min(n, Mi - eb);
+    if (cnt <= 0) return;  // wave-uniform
+    tile_fence();
+    const uint32_t tot = tile_halfsum(tile, lane);
+    if ((int)(lane & 7u) < cnt) {
+      if constexpr (PULL) sc.wpart[((size_t)(r >> 6) * M + (uint32_t)eb) * 8u + wlane] = tot;
+      else (wrow + (size_t)eb * 8u)[wlane] = tot;
     }
+    tile_fence();
+  };
+  // share block b is in ms; q0, q1: the half element carried from block b-1
+  auto fuse_top = [&](uint32_t b, uint32_t q0, uint32_t q1) __attribute__((always_inline)) {
+    const int e0 = 21 * (int)(b >> 1);
+    if ((b & 1) == 0) {
+      if (b) flush(e0 - 5, 5);
+#pragma unroll
+      for (int t = 0; t < 8; t++) stage(e0 + t, t, mword(4 * t));
+    } else {
+      stage(e0 + 10, 2, mk128(q0, q1, kword(ms, 0), kword(ms, 1)));
+#pragma unroll
+      for (int t = 0; t < 5; t++) stage(e0 + 11 + t, 3 + t, mword(2 + 4 * t));
+    }
+  };
+  auto fuse_mid = [&](uint32_t b) __attribute__((always_inline)) {
+    const int e0 = 21 * (int)(b >> 1);
+    if ((b & 1) == 0) {
+      flush(e0, 8);
+      stage(e0 + 8, 0, mword(32));
+      stage(e0 + 9, 1, mword(36));
+    } else {
+      flush(e0 + 8, 8);
+#pragma unroll
+      for (int t = 0; t < 5; t++) stage(e0 + 16 + t, t, mword(22 + 4 * t));
+    }
+  };
+  auto fuse_tail = [&](uint32_t b) __attribute__((always_inline)) {  // b: the last share block
+    const int e0 = 21 * (int)(b >> 1);
+    if ((b & 1) == 0) flush(e0 + 8, 2);
+    else flush(e0 + 16, 5);
   };
   // Joint-rand block b holds the last 42 bytes of share block b-1 (words 0..10, a 16-bit funnel
   // shift) and the first 126 bytes of share block b (words 10..41).  The first part is XORed into
@@ -355,7 +397,7 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
   };
   // block 0: prefix (42 bytes) + the first 126 bytes of the share
   {
-    if (FUSE && fuse) fuse_block(0, 0, 0);
+    if (FUSE && fuse) fuse_top(0, 0, 0);
     squeeze_meas<TR>(p, ms, 0, M, pend0, pend1, sc.meas, r, flag, ts);
     Msg m;
     msg_zero(m);
@@ -370,6 +412,7 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
     for (int j = 11; j < 42; j++)
       kxor_word(js, j, __builtin_amdgcn_alignbit(kword(ms, j - 10), kword(ms, j - 11), 16));
     keccak_p12(js);
+    if (FUSE && fuse) fuse_mid(0);
     carry_tail(B == 1);
     keccak_p12(ms);
   }
@@ -396,13 +439,14 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
       if (q0 < q1) pc0 = lsrc[64 * (size_t)q0];
       if (q0 + 1 < q1) pc1 = lsrc[64 * (size_t)(q0 + 1)];
     }
-    if (FUSE && fuse) fuse_block(b, pend0, pend1);
+    if (FUSE && fuse) fuse_top(b, pend0, pend1);
     squeeze_meas<TR>(p, ms, b, M, pend0, pend1, sc.meas, r, flag, ts);
     kxor_word(js, 10, kword(ms, 0) << 16);
 #pragma unroll
     for (int j = 11; j < 42; j++)
       kxor_word(js, j, __builtin_amdgcn_alignbit(kword(ms, j - 10), kword(ms, j - 11), 16));
     keccak_p12(js);
+    if (FUSE && fuse) fuse_mid(b);
     carry_tail(b + 1 == B);
     if (b + 1 < K) keccak_p12(ms);
     if constexpr (PULL) {
@@ -414,7 +458,7 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
   uint32_t part[4];
   {
     const bool hasW = B < K;
-    if (FUSE && fuse && hasW) fuse_block(B, pend0, pend1);
+    if (FUSE && fuse && hasW) fuse_top(B, pend0, pend1);
     if (hasW) squeeze_meas<TR>(p, ms, B, M, pend0, pend1, sc.meas, r, flag, ts);
 #pragma unroll
     for (int j = 0; j < 42; j++) {
@@ -428,6 +472,10 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
       kxor_word(js, j, x);
     }
     keccak_p12(js);
+    if (FUSE && fuse) {  // the last share block is B, or B-1 (its fuse_mid has run in the loop)
+      if (hasW) fuse_mid(B);
+      fuse_tail(hasW ? B : B - 1);
+    }
     part[0] = kword(js, 0);
     part[1] = kword(js, 1);
     part[2] = kword(js, 2);
@@ -486,7 +534,7 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
   }
 }
 template <bool FUSE, bool TR = false>
-__global__ __launch_bounds__(256, XOFD_OCC) void k_xofd(DevParams p, InPtrs in, Scratch sc) {
+__global__ __launch_bounds__(XOFD_BLOCK, XOFD_OCC) void k_xofd(DevParams p, InPtrs in, Scratch sc) {
   xofd_body<FUSE, TR>(p, in, sc, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
@@ -1881,7 +1929,7 @@ __global__ __launch_bounds__(256, 3) void k_query_h(DevParams p, InPtrs in, Scra
 // without a kernel boundary, a second stream or the k_xof_slow launch between them.  The query
 // reads the scratch rows its own lane has just written.
 template <bool FUSE, bool PULL = false>
-__global__ __launch_bounds__(256, 3) void k_prep_h(DevParams p, InPtrs in, Scratch sc,
+__global__ __launch_bounds__(XOFD_BLOCK, 3) void k_prep_h(DevParams p, InPtrs in, Scratch sc,
                                                    OutPtrs out) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   xofd_body<FUSE, false, PULL>(p, in, sc, r);
@@ -2581,6 +2629,23 @@ __global__ void k_selftest_f128(int op, uint32_t n, const uint4* a, const uint4*
   out[i] = make_uint4(z.w[0], z.w[1], z.w[2], z.w[3]);
 }
 
+// The fused accumulate's tile reduction (tile_stage / tile_halfsum) on caller-supplied values:
+// one wave stages all FTILE slots from in [FTILE][64][16 B] (slot, lane) and writes the 8 addends
+// of the first cnt slots to out [cnt][8]; the slots from cnt on are staged too and must not count.
+__global__ __launch_bounds__(64) void k_selftest_tile(uint32_t cnt, const uint4* in,
+                                                      uint32_t* out) {
+  __shared__ uint4 tile[FTILE * 64];
+  const uint32_t lane = threadIdx.x;
+#pragma unroll
+  for (int s = 0; s < FTILE; s++) {
+    const uint4 v = in[s * 64 + (int)lane];
+    tile_stage(tile, s, lane, mk128(v.x, v.y, v.z, v.w));
+  }
+  tile_fence();
+  const uint32_t tot = tile_halfsum(tile, lane);
+  if ((lane & 7u) < cnt) out[(lane & 7u) * 8u + (lane >> 3)] = tot;
+}
+
 // ====================================================================================
 // Host side
 // ====================================================================================
@@ -3240,6 +3305,7 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
   if (sc.wseg) sc.wseg += c0 / 64;
   if (sc.wpart) sc.wpart += (size_t)(c0 / 64) * dp.meas_len * 8;
   const uint32_t blocks = (n + 255) / 256;
+  const uint32_t xblocks = (n + XOFD_BLOCK - 1) / XOFD_BLOCK;  // k_prep_h, k_xofd
   if (dp.kind == PRIO3_SUMVEC_F64_MP) {
     int rc = PRIO3_OK;
     TIMED(e, st, "k_mp64_prepare", (rc = launch_mp64(e, n, dp.ld, in, out, sc, st)));
@@ -3277,7 +3343,9 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
       bool paired = false;
       if (dual) TIMED(e, st, "k_xof_pair", (paired = launch_xof_pair(q, qi, qs, st)));
       if (!paired && dual)
-        TIMED(e, st, "k_xofd", (k_xofd<false, true><<<qb, 256, 0, st>>>(q, qi, qs)));
+        TIMED(e, st, "k_xofd",
+              (k_xofd<false, true><<<(q.n + XOFD_BLOCK - 1) / XOFD_BLOCK, XOFD_BLOCK, 0, st>>>(
+                  q, qi, qs)));
       else if (!paired)
         TIMED(e, st, "k_xof", (k_xof<Fp128><<<qb, 256, 0, st>>>(q, qi, qs)));
       TIMED(e, st, "k_xof_slow", launch_xof_slow<Fp128>(e, q, qi, qs, st));
@@ -3316,13 +3384,13 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
           TIMED(e, st, "k_prep_hp", (paired = launch_prep_pair(dp, in, sc, out, st, fuse, pl)));
         if (paired) {
         } else if (fuse && pl)
-          TIMED(e, st, "k_prep_h", (k_prep_h<true, true><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+          TIMED(e, st, "k_prep_h", (k_prep_h<true, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
         else if (fuse)
-          TIMED(e, st, "k_prep_h", (k_prep_h<true><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+          TIMED(e, st, "k_prep_h", (k_prep_h<true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
         else if (pl)
-          TIMED(e, st, "k_prep_h", (k_prep_h<false, true><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+          TIMED(e, st, "k_prep_h", (k_prep_h<false, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
         else
-          TIMED(e, st, "k_prep_h", (k_prep_h<false><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+          TIMED(e, st, "k_prep_h", (k_prep_h<false><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
       }
       return PRIO3_OK;
     }
@@ -3330,11 +3398,11 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
     // k_xof_a + k_jrpart), then the query
     if (dual) {
       if (fuse)
-        TIMED(e, st, "k_xofd", (k_xofd<true><<<blocks, 256, 0, st>>>(dp, in, sc)));
+        TIMED(e, st, "k_xofd", (k_xofd<true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
       else if (dp.trunc_xof)
-        TIMED(e, st, "k_xofd", (k_xofd<false, true><<<blocks, 256, 0, st>>>(dp, in, sc)));
+        TIMED(e, st, "k_xofd", (k_xofd<false, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
       else
-        TIMED(e, st, "k_xofd", (k_xofd<false><<<blocks, 256, 0, st>>>(dp, in, sc)));
+        TIMED(e, st, "k_xofd", (k_xofd<false><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
     } else {
       TIMED(e, st, "k_xof_a", (k_xof_a<Fp128><<<blocks, 256, 0, st>>>(dp, in, sc)));
       TIMED(e, st, "k_jrpart", (k_jrpart<false><<<blocks, 256, 0, st>>>(dp, in, sc)));
@@ -5520,6 +5588,25 @@ int prio3_selftest_field(int op, uint32_t n, const uint8_t* a, const uint8_t* b,
   }
   (void)hipFree(da);
   (void)hipFree(db);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int prio3_selftest_tile(uint32_t n_elems, const uint8_t* values, uint32_t* out) {
+  if (n_elems == 0 || n_elems > (uint32_t)FTILE || !values || !out) return PRIO3_EINVAL;
+  const size_t m = (size_t)FTILE * 64 * 16, mo = (size_t)n_elems * 8 * sizeof(uint32_t);
+  void *din = nullptr, *dout = nullptr;
+  int rc = PRIO3_OK;
+  if (hipMalloc(&din, m) != hipSuccess || hipMalloc(&dout, mo) != hipSuccess ||
+      hipMemcpy(din, values, m, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = PRIO3_EDEVICE;
+  } else {
+    k_selftest_tile<<<1, 64>>>(n_elems, (const uint4*)din, (uint32_t*)dout);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(out, dout, mo, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = PRIO3_EDEVICE;
+  }
+  (void)hipFree(din);
   (void)hipFree(dout);
   return rc;
 }

@@ -109,7 +109,7 @@ EXPORTED_SYMBOLS = (
     "prio3_helper_aggregate_init_batch_ex",
     "prio3_leader_prepare_next_aggregate_batch",
     "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
-    "prio3_client_rand_len", "prio3_client_report_stride",
+    "prio3_client_rand_len", "prio3_client_report_stride", "prio3_selftest_tile",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -182,6 +182,7 @@ def load_library() -> C.CDLL:
     L.prio3_engine_timing_reset.argtypes = [vp]
     L.prio3_engine_timing_reset.restype = None
     L.prio3_selftest_field.argtypes = [C.c_int, C.c_uint32, vp, vp, vp]
+    L.prio3_selftest_tile.argtypes = [C.c_uint32, vp, vp]
     L.prio3_trace_enabled.argtypes = []
     L.prio3_device_trim.argtypes = [C.c_int]
     L.prio3_device_prepare_aggregate.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32,
@@ -224,6 +225,18 @@ def selftest_field(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     rc = load_library().prio3_selftest_field(op, n, _np_ptr(a), _np_ptr(b), _np_ptr(out))
     if rc:
         raise RuntimeError(f"prio3_selftest_field failed (rc={rc})")
+    return out
+
+
+def selftest_tile(values: np.ndarray, n_elems: int) -> np.ndarray:
+    """Test hook: the fused accumulate's tile reduction over uint8 [8, 64, 16] (slot, lane, LE
+    bytes); returns uint32 [n_elems, 8], the 16-bit-weighted addends of each slot's wave sum."""
+    values = np.ascontiguousarray(values, np.uint8)
+    assert values.shape == (8, 64, 16)
+    out = np.zeros((n_elems, 8), np.uint32)
+    rc = load_library().prio3_selftest_tile(n_elems, _np_ptr(values), _np_ptr(out))
+    if rc:
+        raise RuntimeError(f"prio3_selftest_tile failed (rc={rc})")
     return out
 
 
