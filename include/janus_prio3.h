@@ -461,7 +461,7 @@ int prio3_device_trim(int device);
 /* force_slow_path=1 routes every report through the general rejection-sampling kernel;
  * leader_fuse_acc=0 turns off the fused device-leader accumulate (A/B); pair_max=N runs
  * Histogram(P = 32) prepares of at most N reports on lane pairs (0: never); the other keys are
- * the launch variants prio3_engine.hip's prio3_engine_set_option lists. */
+ * the launch variants prio3_engine_set_option (prio3_engine.hip) lists. */
 int prio3_engine_set_option(prio3_engine* engine, const char* key, int64_t value);
 /* Per-kernel device time (ms) accumulated since the last reset, measured with HIP events
  * on the launch stream when option "timing" is 1 (2: launches counted, no events or times).

@@ -21,6 +21,7 @@
 #include "../../include/janus_dap.h"
 #include "../../include/janus_hpke.h"
 #include "prio3_common.h"
+#include "prio3_host.h"
 #include "prio3_runtime.h"
 #include "prio3_mp64_xof.h"
 

@@ -1,5 +1,6 @@
 // prio3_common.h -- kernel-side structures and per-lane building blocks shared by the
-// helper engine (prio3_engine.hip) and the synthetic client (prio3_client.hip).
+// helper engine (prio3_prepare.hip, prio3_accumulate.hip, prio3_engine.hip) and the synthetic
+// client (prio3_client.hip).
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -558,7 +559,7 @@ u128 hpow(u128 a, u128 e, u128 p) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------
-// Host-side engine object (shared by both translation units)
+// Host-side engine object (shared by every translation unit)
 // ------------------------------------------------------------------------------------
 struct KTime {
   std::string name;
@@ -619,8 +620,6 @@ struct Run {
   Scratch sc{};
   uint8_t *nonces = nullptr, *pub = nullptr, *helper = nullptr, *leader = nullptr,
           *linput = nullptr, *msgs = nullptr, *status = nullptr;
-  uint16_t* vk_slot = nullptr;
-  uint4* vk_tab = nullptr;
   // fused accumulate (prio3_device_prepare_aggregate)
   uint32_t *wpart = nullptr, *wseg = nullptr, *cseg = nullptr, *fix = nullptr;
   uint4* corr_all = nullptr;  // FPVec: corrected joint-rand seeds of all n reports (leader)
@@ -682,7 +681,6 @@ struct prio3_engine {
   uint64_t* d_sigma64 = nullptr;
   uint4* d_sigma128 = nullptr;  // k_query_w's sigma table (DevParams::sigma_dev)
   std::vector<KTime> times;
-  std::vector<hipEvent_t> ev_pool;
   std::mutex tmu;  // timing bookkeeping (launches may come from several executor threads)
   std::mutex mu;   // device-resident calls, `cur`, side streams
   // ---- one engine over several GPUs (prio3_engine_create_devices / _mask) ----

@@ -1,0 +1,151 @@
+// prio3_host.h -- host-only declarations shared by the three engine translation units:
+//   prio3_prepare.hip     helper / leader prepare kernels and their launch plans
+//   prio3_accumulate.hip  accumulate, aggregate, combine and metadata kernels and launches
+//   prio3_engine.hip      sizes, timing, runs, executor hooks and the C ABI
+// (prio3_client.hip includes it for the leader launch declarations.)  Device-only headers and the
+// kernel families with a launch_* function of their own (prio3_common.h) do not include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <vector>
+
+#include "prio3_common.h"
+#include "prio3_runtime.h"
+
+#define HIPCHK(x)                                                                   \
+  do {                                                                              \
+    hipError_t _e = (x);                                                            \
+    if (_e != hipSuccess) {                                                         \
+      fprintf(stderr, "janus_prio3: HIP error %s at %s:%d\n", hipGetErrorString(_e), \
+              __FILE__, __LINE__);                                                  \
+      return PRIO3_EDEVICE;                                                         \
+    }                                                                               \
+  } while (0)
+
+// ---- per-kernel timing (option "timing"): HIP events on the launch stream ----
+// One list per thread for the whole library, defined in prio3_engine.hip: collect_times folds
+// the events of every unit's launches.
+struct Pending {
+  prio3_engine* e;
+  size_t idx;
+  hipEvent_t a, b;
+};
+std::vector<Pending>& pending();
+size_t time_slot(prio3_engine* e, const char* name);
+// timing 2: launches are counted only (no events on the production launch path)
+void count_launch(prio3_engine* e, const char* name);
+// folds this thread's finished timing events of engine e into e->times.  wait = false (the
+// executor's group finish): events still pending -- those of the group issued ahead behind the
+// finishing one -- are left for a later call instead of blocking the launcher on them
+void collect_times(prio3_engine* e, bool wait = true);
+#define TIMED(e, st, name, launch)                                   \
+  do {                                                               \
+    hipEvent_t _a = nullptr, _b = nullptr;                           \
+    const bool _t = (e)->timing == 1 && hipEventCreate(&_a) == hipSuccess && \
+                    hipEventCreate(&_b) == hipSuccess;               \
+    if (_t) (void)hipEventRecord(_a, st);                            \
+    launch;                                                          \
+    HIPCHK(hipGetLastError());                                       \
+    if (_t) {                                                        \
+      (void)hipEventRecord(_b, st);                                  \
+      pending().push_back(Pending{(e), time_slot(e, name), _a, _b}); \
+    } else if ((e)->timing == 2) {                                   \
+      count_launch((e), name);                                       \
+    }                                                                \
+  } while (0)
+
+// ---- runs: the device state of one prepare call, carved from one pooled slab ----
+enum : unsigned {
+  RUN_SCRATCH = 1,  // SoA prepare scratch
+  RUN_IO = 2,       // device copies of host inputs / outputs (host-buffer entry points)
+  RUN_LINPUT = 8,   // leader input shares (host-buffer leader entry point)
+  RUN_FUSED = 16,   // fused-accumulate partials (prio3_device_prepare_aggregate, Histogram)
+  RUN_AGG_IO = 32,  // group segment ids, accept bytes, aggregate shares + counts (executor)
+  RUN_HPKE = 64,    // open statuses + plaintext scratch of a sealed-input group (executor)
+};
+
+static inline bool own_out(const DevParams& d) {  // the output share is not the measurement share
+  return d.kind == PRIO3_SUM || d.kind == PRIO3_SUMVEC || d.kind == PRIO3_SUMVEC_F64_MP ||
+         d.kind == PRIO3_FPVEC_BOUNDED_L2;
+}
+// the run's output shares at column c0 (SoA [element][ld_out])
+static inline const uint8_t* run_out_shares(const Run* R, uint32_t c0) {
+  return (const uint8_t*)(own_out(R->dp) ? R->sc.out : R->sc.meas) + (size_t)R->dp.es * c0;
+}
+
+constexpr uint32_t WCH = 32;  // waves per fused-partial chunk (k_agg_waves, run_carve)
+
+// a pooled stream for one blocking host-buffer call
+struct PooledStream {
+  int device;
+  hipStream_t s;
+  explicit PooledStream(int dev) : device(dev), s(ws_stream_get(dev)) {}
+  ~PooledStream() { ws_stream_put(device, s); }
+};
+
+// Copies by the shader cores between device memory and mapped pinned memory (up to 4 ranges,
+// 16-byte aligned; 16-byte accesses, the byte tails by lane).  Host -> device, this reads PCIe at
+// ~55 GB/s where the SDMA copy of the same staging ran at ~32 GB/s beside the XOF's own host
+// reads (profiles/r03/r03l trace); device -> host, one launch returns a group's four outputs
+// where four SDMA copies each paid their own setup.
+struct PullRanges {
+  const uint8_t* src[4];
+  uint8_t* dst[4];
+  size_t bytes[4];
+};
+// k_pull (prio3_engine.hip) over `blocks` blocks; false if the launch failed
+bool launch_pull(const PullRanges& pr, unsigned blocks, hipStream_t st);
+
+// ---- prio3_prepare.hip (described at their definitions) ----
+bool fusable(const prio3_engine* e);
+bool leader_fuse_takes(const prio3_engine* e);
+bool leader_prep_takes(const prio3_engine* e);
+// the helper's kernel chain over the whole run
+int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st, bool fuse,
+                bool allow_chunks, const PullRanges* pull = nullptr);
+// the leader's prepare_init (agg_id 0) over the run; lin_ld: InPtrs::lin_ld
+int leader_init_run(prio3_engine* e, Run* R, const uint8_t* d_nonces,
+                    const uint8_t* d_public_shares, const uint8_t* d_leader_input_shares,
+                    uint8_t* d_prep_shares, uint8_t* d_status, hipStream_t st,
+                    const uint16_t* vk_slot = nullptr, const uint4* vk_tab = nullptr,
+                    uint32_t lin_ld = 0);
+
+// ---- prio3_accumulate.hip ----
+// One-pass segmented accumulate over columns [c0, c0 + n) of a run: d_status[n] (the run's
+// verdicts for those columns), d_seg[n] (nullable: segment 0), d_accept[n] (nullable: all
+// accepted); d_agg[nseg][out_len * es], d_counts[nseg].
+int run_accumulate(prio3_engine* e, Run* R, uint32_t c0, uint32_t n, const uint8_t* d_status,
+                   const uint32_t* d_seg, const uint8_t* d_accept, uint32_t nseg, uint8_t* d_agg,
+                   uint64_t* d_counts, hipStream_t st);
+int fused_finish(prio3_engine* e, Run* R, const uint8_t* d_status, const uint32_t* seg,
+                 const uint32_t* fix_seg, const uint8_t* d_accept_mask, uint32_t S,
+                 uint8_t* d_agg_shares, uint64_t* d_counts, hipStream_t st);
+// The accumulate of a group of n_jobs jobs (descriptors, segment ids and accept bytes staged in
+// `host` as AccLayout lays them out) enqueued on st: the staged inputs into a device area from
+// the scratch pool, k_acc_multi, the first out_bytes of the outputs back into `host`.  Returns
+// the area (the caller releases it after the stream), or nullptr with *rc set.
+Slab* acc_multi_enqueue(int device, uint32_t es, uint8_t* host, const AccLayout& L,
+                        uint32_t n_jobs, size_t out_bytes, hipStream_t st, int* rc);
+int launch_combine(prio3_engine* e, uint32_t k, uint32_t n_segments, const uint8_t* d_in,
+                   const uint64_t* d_counts_in, uint8_t* d_out, uint64_t* d_counts_out,
+                   hipStream_t st);
+int launch_batch_metadata(prio3_engine* e, uint32_t n, const uint8_t* d_report_ids,
+                          const uint64_t* d_times, const uint8_t* d_status,
+                          const uint8_t* d_accept_mask, const uint32_t* d_segment_ids,
+                          uint32_t n_segments, uint32_t* ck, unsigned long long* iv,
+                          hipStream_t st);
+int launch_combine_metadata(prio3_engine* e, uint32_t k, uint32_t n_segments,
+                            const uint32_t* ck_in, const unsigned long long* iv_in,
+                            uint32_t* ck_out, unsigned long long* iv_out, hipStream_t st);
+
+// ---- prio3_client.hip: the generic leader kernels ----
+extern "C" int launch_leader_init(const DevParams& dp, const uint8_t* d_nonces,
+                                  const uint8_t* d_pub, const uint8_t* d_lshares,
+                                  const Scratch& sc, uint8_t* d_prep_shares, uint8_t* d_status,
+                                  hipStream_t st, const uint16_t* vk_slot, const uint4* vk_tab);
+extern "C" int launch_leader_next(const DevParams& dp, const uint8_t* d_prep_msgs,
+                                  const Scratch& sc, uint8_t* d_status, hipStream_t st);
+extern "C" int launch_leader_next_multi(uint32_t es, const LNextDesc* d_desc,
+                                        const uint8_t* d_msgs, uint8_t* d_status, uint32_t n_jobs,
+                                        uint32_t max_n, hipStream_t st);

@@ -42,7 +42,7 @@ DEV T pair_x(const T& a) { return mk128(pair_x(a.w[0]), pair_x(a.w[1]), pair_x(a
 DEV T sel(bool c, const T& a, const T& b) { return F::sel(c, a, b); }
 
 // ---- the query of one report on its lane pair (h = 0 even, 1 odd); both lanes active --------
-// The one-lane form is query_h_body<2, 32> (prio3_engine.hip); this splits its work in halves.
+// The one-lane form is query_h_body<2, 32> (prio3_prepare.hip); this splits its work in halves.
 // PAIR_GS: wires per sweep of the wire loop (each sweep re-reads the 16 beta_k and L_k); 2 keeps
 // four lazy 128-bit MAC accumulators (21 VGPRs each) live.  PAIR_DIRECT_BETA: the beta_k are
 // formed and stored as the Lagrange phases produce their L values (r^C taken first), instead of

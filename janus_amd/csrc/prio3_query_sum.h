@@ -1,5 +1,5 @@
 // prio3_query_sum.h -- the Prio3Sum helper/leader query body (k_query_sum, prio3_query_sum.hip),
-// shared with the fused XOF + query kernel of prio3_engine.hip (k_prep_sum).  See
+// shared with the fused XOF + query kernel of prio3_prepare.hip (k_prep_sum).  See
 // prio3_query_sum.hip for the algorithm.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,7 +49,7 @@ DEV void geo16(T (&x)[16], T s, const T& q) {
 // out.prep_msgs (stride prep_share_len) instead of being decided against a peer's share;
 // out.status holds the unpack verdict on entry.
 // slow_defer / redo (DevParams): as query_h_body -- a flagged report is skipped here and redone
-// by the run's k_slow_redo launch (prio3_engine.hip)
+// by the run's k_slow_redo launch (prio3_prepare.hip)
 template <int NPH, int LEADER = 0>
 __device__ __forceinline__ void query_sum_body(const DevParams& p, const InPtrs& in,
                                                const Scratch& sc, const OutPtrs& out,

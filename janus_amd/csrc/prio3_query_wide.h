@@ -1,6 +1,6 @@
 // prio3_query_wide.h -- the eight-lanes-per-report ParallelSum(Mul) query body (k_query_w,
-// prio3_query_wide.hip), shared with the fused XOF + query kernel of prio3_engine.hip
-// (k_prep_w).  See prio3_query_wide.hip for the algorithm.
+// prio3_query_wide.hip), which launch_prepare (prio3_prepare.hip) runs after the XOF.  See
+// prio3_query_wide.hip for the algorithm.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,7 +5,7 @@
 //
 // prio 0.16.2 FlpGeneric::query + decide, helper side of
 // Prio3::prepare_init / prepare_shares_to_prepare_message; call site helper_initialized,
-// aggregator.rs:2020-2042.  Same arithmetic as k_query_ps (prio3_engine.hip) -- wire 2j of call k
+// aggregator.rs:2020-2042.  Same arithmetic as k_query_ps (prio3_prepare.hip) -- wire 2j of call k
 // carries r^(Ck+j+1) m_(Ck+j), wire 2j+1 carries m_(Ck+j) - 1/2 -- laid out for the machine:
 //
 // * one lane per report (k_query_ps) spends ~3 M VALU instructions per SumVec 8x1000 report

@@ -298,7 +298,7 @@ struct LeaderLayout {
 void engine_leader_layout(const prio3_engine* e, uint32_t cap, LeaderLayout* L);
 // one DMA of the staged inputs into the run, the leader kernels, the outputs back into the staging
 int engine_leader_issue(prio3_engine* lead, const LeaderLayout& L, uint8_t* stg, uint8_t* stg_dev,
-                        uint32_t n, uint32_t n_keys, int jobs, GroupRun* gr, bool own_queue);
+                        uint32_t n, int jobs, GroupRun* gr, bool own_queue);
 int exec_leader(LeaderJob* job);
 
 // ---- coalesced leader prepare_next (prio3_leader_prepare_next_batch of concurrent jobs) -------

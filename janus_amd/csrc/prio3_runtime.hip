@@ -1265,8 +1265,7 @@ struct LeaderPolicy {
   };
   static int issue(int, State& s, Staging& g, Handle* h, bool own_queue) {
     h->s = &s;
-    return engine_leader_issue(s.lead, s.L, g.p, g.dev, s.n, (uint32_t)s.keys.size(),
-                               (int)s.jobs, &h->gr, own_queue);
+    return engine_leader_issue(s.lead, s.L, g.p, g.dev, s.n, (int)s.jobs, &h->gr, own_queue);
   }
   static bool prepared(const Handle& h) { return engine_group_prepared(h.gr); }
   static bool done(const Handle& h) { return engine_group_done(h.gr); }

@@ -1,5 +1,5 @@
 // sha256_device.h -- SHA-256 compression (FIPS 180-4) for one message block per work-item.
-// Used for ReportIdChecksum (prio3_engine.hip, k_meta) and for HMAC/HKDF-SHA256 of the HPKE
+// Used for ReportIdChecksum (prio3_accumulate.hip, k_meta) and for HMAC/HKDF-SHA256 of the HPKE
 // key schedule (hpke.hip).  Fully unrolled: the round constants become instruction literals.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 """Static VALU instruction mix of the engine's kernels, from the gfx950 assembly.
 
-Usage: python tools/isa_mix.py [--asm FILE] [--kernel SUBSTR]
-  (without --asm the engine is compiled with `hipcc --cuda-device-only -S` into /tmp)
+Usage: python tools/isa_mix.py [--asm FILE] [--source FILE.hip] [--kernel SUBSTR]
+  (without --asm the source -- by default prio3_prepare.hip, the prepare kernels -- is compiled
+  with `hipcc --cuda-device-only -S` into /tmp)
 
 For every kernel it prints the VALU instructions of the whole kernel and of each loop (a
 `=>This Inner Loop Header` label up to the last branch back to it), split by issue class.
@@ -33,11 +34,12 @@ PEAK_FULL_T = 64.5
 PEAK_HALF_T = 37.0
 
 
-def asm_path(source: str = "prio3_engine.hip"):
+def asm_path(source: str = "prio3_prepare.hip"):
     out = f"/tmp/{source.replace('.hip', '')}_gfx950.s"
     src = os.path.join(ROOT, "janus_amd", "csrc", source)
     deps = [src] + [os.path.join(ROOT, "janus_amd", "csrc", h) for h in
-                    ("prio3_device.h", "prio3_common.h", "sha256_device.h")]
+                    ("prio3_device.h", "prio3_common.h", "prio3_host.h", "prio3_query_sum.h",
+                     "sha256_device.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
                         "--cuda-device-only", "-S", "-o", out, src], check=True)
@@ -109,7 +111,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm")
     ap.add_argument("--kernel", default="")
-    ap.add_argument("--source", default="prio3_engine.hip")
+    ap.add_argument("--source", default="prio3_prepare.hip")
     a = ap.parse_args()
     lines = open(a.asm or asm_path(a.source)).read().splitlines()
     for k, body in split_kernels(lines).items():

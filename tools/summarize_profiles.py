@@ -74,7 +74,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import isa_mix
     asm = {}
-    for source in ("prio3_engine.hip", "hpke.hip"):
+    for source in ("prio3_prepare.hip", "prio3_accumulate.hip", "prio3_engine.hip", "hpke.hip"):
         asm.update(isa_mix.split_kernels(open(isa_mix.asm_path(source)).read().splitlines()))
     ceilings = {}
     for k, body in asm.items():
