@@ -240,7 +240,7 @@ int janus_dap_agg_job_resp_unpack_device(uint32_t n, const uint32_t* d_index,
  * Device form: runs on `stream` of the GPU that owns d_out without host synchronisation; the
  * calling thread's current device is left as it was.  Host form: returns the number of reports
  * written (rows with out_len != 0) or JANUS_DAP_EARG.  The decoding direction (the leader's upload
- * handler) is not provided. */
+ * handler) is janus_dap_report_decode_* below. */
 size_t janus_dap_report_max_len(uint32_t public_share_len, uint32_t leader_enc_len,
                                 uint32_t leader_ct_stride, uint32_t helper_enc_len,
                                 uint32_t helper_ct_stride);
@@ -264,6 +264,55 @@ int64_t janus_dap_report_encode_host(uint32_t n, const uint8_t* report_ids, cons
                                      const uint32_t* helper_ct_len, uint32_t helper_ct_stride,
                                      const uint8_t* skip, uint8_t* out, uint32_t out_stride,
                                      uint32_t* out_len);
+
+/* ---- Leader side: the upload body, decoded ----------------------------------------------------
+ * The inverse of janus_dap_report_encode_*, for the leader's upload handler
+ * (`Report::get_decoded`, aggregator.rs handle_upload_generic): the same row form as input,
+ * reports[n][report_stride] with report_len[n], one uploaded body per row.  Per report:
+ *   report_ids[n][16], times[n], leader_config_ids[n], helper_config_ids[n],
+ *   fields[n][JANUS_DAP_REPORT_FIELDS] (u32): byte offset within the row and length of the public
+ *     share, and of `enc` and the payload of the leader's and the helper's HpkeCiphertext, at the
+ *     JANUS_DAP_REPORT_* indices -- the large fields stay in place in the row,
+ *   the helper's ciphertext copied out as the rows janus_dap_agg_init_req_encode_* reads:
+ *     helper_enc[n][helper_enc_len], helper_ct[n][helper_ct_stride] with helper_ct_len[n] (bytes
+ *     of a row past its payload are zero).  A helper `enc` of another length than helper_enc_len,
+ *     or a payload above helper_ct_stride, gives helper_ct_len 0 and zero rows (the helper fails
+ *     that report's HPKE open); fields[] still holds the lengths found.
+ *   malformed[n]: 1 when the Report does not decode -- a length prefix runs past report_len, bytes
+ *     trail the second ciphertext, or report_len > report_stride.  Every output of such a report is
+ *     zero.  A public share or `enc` of an unexpected length is not malformed here.
+ * No byte past report_len or report_stride is read.  helper_enc_len above 0xFFFF, a report_stride
+ * of 2^31 or more, or a missing buffer is JANUS_DAP_EARG.
+ * Host form: needs no GPU; returns the number of reports that decoded, or JANUS_DAP_EARG.
+ * Device form: runs on `stream` of the GPU that owns d_malformed without host synchronisation; the
+ * calling thread's current device is left as it was. */
+#define JANUS_DAP_REPORT_FIELDS 10
+enum {
+  JANUS_DAP_REPORT_PUBLIC_SHARE_OFF = 0,
+  JANUS_DAP_REPORT_PUBLIC_SHARE_LEN = 1,
+  JANUS_DAP_REPORT_LEADER_ENC_OFF = 2,
+  JANUS_DAP_REPORT_LEADER_ENC_LEN = 3,
+  JANUS_DAP_REPORT_LEADER_PAYLOAD_OFF = 4,
+  JANUS_DAP_REPORT_LEADER_PAYLOAD_LEN = 5,
+  JANUS_DAP_REPORT_HELPER_ENC_OFF = 6,
+  JANUS_DAP_REPORT_HELPER_ENC_LEN = 7,
+  JANUS_DAP_REPORT_HELPER_PAYLOAD_OFF = 8,
+  JANUS_DAP_REPORT_HELPER_PAYLOAD_LEN = 9
+};
+int64_t janus_dap_report_decode_host(uint32_t n, const uint8_t* reports, uint32_t report_stride,
+                                     const uint32_t* report_len, uint8_t* report_ids,
+                                     uint64_t* times, uint32_t* fields, uint8_t* leader_config_ids,
+                                     uint8_t* helper_config_ids, uint8_t* helper_enc,
+                                     uint32_t helper_enc_len, uint8_t* helper_ct,
+                                     uint32_t* helper_ct_len, uint32_t helper_ct_stride,
+                                     uint8_t* malformed);
+int janus_dap_report_decode_device(uint32_t n, const uint8_t* d_reports, uint32_t report_stride,
+                                   const uint32_t* d_report_len, uint8_t* d_report_ids,
+                                   uint64_t* d_times, uint32_t* d_fields,
+                                   uint8_t* d_leader_config_ids, uint8_t* d_helper_config_ids,
+                                   uint8_t* d_helper_enc, uint32_t helper_enc_len,
+                                   uint8_t* d_helper_ct, uint32_t* d_helper_ct_len,
+                                   uint32_t helper_ct_stride, uint8_t* d_malformed, void* stream);
 
 #ifdef __cplusplus
 }

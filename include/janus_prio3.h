@@ -369,6 +369,86 @@ int prio3_device_leader_prepare_next(prio3_engine* engine, uint32_t n, const uin
  * with n_segments == 1 finishes from them (the verdicts, the accept mask and out-of-range
  * segment ids are applied as corrections), any other accumulate reads the output shares. */
 
+/* ---- Leader upload ---- */
+/* The leader's upload handler for a batch of one task (VdafOps::handle_upload_generic,
+ * aggregator/src/aggregator.rs:1522-1702; Janus batches the stored reports in ReportWriteBatcher):
+ * from the uploaded `Report` bodies -- the rows prio3_client_prepare_reports_device writes,
+ * reports[n][report_stride] with report_len[n] -- to the buffers the leader's prepare reads, with no
+ * host parsing and no host cryptography.  Per report, the first failing check decides status[r]:
+ *   1. the Report decodes (janus_dap_report_decode_*), else PRIO3_UPLOAD_MALFORMED (the handler's
+ *      Error::MessageDecode, not a rejection);
+ *   2. time > report_deadline (= now + tolerable clock skew, the caller's)   -> TooEarly (:1559)
+ *   3. time > task_expiration (UINT64_MAX: none)                             -> TaskExpired (:1565)
+ *   4. now > time + report_expiry_age (UINT64_MAX: none)                     -> Expired (:1572);
+ *      a sum that overflows a u64 is PRIO3_UPLOAD_HOST (the reference's internal error)
+ *   5. the public share's length is not prio3_sizes' public_share_len      -> DecodeFailure (:1588)
+ *   6. the leader ciphertext's config ID is neither opener's  -> OutdatedHpkeConfig (:1626); the
+ *      leader config IDs are written out so that the host can name the ID
+ *   7. HPKE open over InputShareAad { task_id, metadata, public share } (built on the device) with
+ *      the opener of that config ID; when both have it, the task's first and the global one only
+ *      for a report whose open failed (:1637-1644)                         -> DecryptFailure
+ *      (also: an `enc` that is not the KEM's Nenc bytes, a payload below 16 bytes)
+ *   8. PlaintextInputShare::get_decoded and the Prio3 leader share (:1661-1686): the u16-prefixed
+ *      extension list { u16 type, u16-prefixed data } is well formed (the codec's ExtensionType
+ *      knows Tbd = 0 and Taskprov = 0xFF00; duplicates and the like are not the handler's), the
+ *      u32-prefixed payload ends the plaintext, has leader_input_share_len bytes, and every field
+ *      element of the measurement and proofs shares is canonical (LE Field128; Field64 for
+ *      PRIO3_SUMVEC_F64_MP)                                                 -> DecodeFailure
+ *   then PRIO3_UPLOAD_HOST when the extension bytes do not fit ext_stride: the host handles that
+ *   report itself.
+ * The codes are Janus's ReportRejectionReason in the order of aggregator/error.rs:220-228, from 1;
+ * IntervalCollected is never produced here (that check stays in the writer's transaction).
+ * Both openers (janus_hpke.h; either may be NULL, not both) are created with the info
+ * "dap-09 input share" || 0x01 || 0x02 and are bound to the engine's GPU.
+ * Outputs: report_ids[n][16], times[n], public_shares[n][public_share_len] (NULL when that is 0),
+ * leader_input_shares[n][leader_input_share_len] -- what prio3_leader_prepare_init_batch /
+ * prio3_device_leader_prepare_init read; extensions[n][ext_stride] with ext_len[n] (the encoded
+ * list body, as LeaderStoredReport keeps it); the helper's ciphertext as the rows
+ * janus_dap_agg_init_req_encode_* reads (helper_config_ids[n], helper_enc[n][helper_enc_len],
+ * helper_ct[n][helper_ct_stride], helper_ct_len[n]; janus_dap.h); leader_config_ids[n]; status[n].
+ * Every row of a report with a non-zero status is zero (its leader config ID excepted, unless the
+ * Report is malformed), and a failed open leaves no plaintext behind, in scratch either.
+ * PRIO3_EINVAL: both openers NULL, an opener on another GPU than the engine, report_stride or
+ * ext_stride not a multiple of 4 (d_reports 4-byte aligned), a missing buffer.
+ * PRIO3_FPVEC_BOUNDED_L2 returns PRIO3_EUNSUPPORTED.  Engine option upload_aead: 0 chooses the AEAD
+ * kernel by the instance's payload length, 1 forces the one-lane body of the helper's open, 2 the
+ * 16-lanes-per-report AES-GCM kernel; ChaCha20Poly1305 always takes the one-lane body.
+ * Device form: stream-ordered, no host synchronisation, scratch from the GPU's pool (batches above
+ * 65536 reports run in sub-batches on the stream); the calling thread's device is left as it was.
+ * Host form: a plain blocking call. */
+enum {
+  PRIO3_UPLOAD_OK = 0,
+  PRIO3_UPLOAD_INTERVAL_COLLECTED = 1,
+  PRIO3_UPLOAD_DECRYPT_FAILURE = 2,
+  PRIO3_UPLOAD_DECODE_FAILURE = 3,
+  PRIO3_UPLOAD_TASK_EXPIRED = 4,
+  PRIO3_UPLOAD_EXPIRED = 5,
+  PRIO3_UPLOAD_TOO_EARLY = 6,
+  PRIO3_UPLOAD_OUTDATED_HPKE_CONFIG = 7,
+  PRIO3_UPLOAD_MALFORMED = 0x40,
+  PRIO3_UPLOAD_HOST = 0x41,
+};
+int prio3_device_leader_upload(
+    prio3_engine* engine, struct janus_hpke_opener* task_opener, uint8_t task_config_id,
+    struct janus_hpke_opener* global_opener, uint8_t global_config_id, uint32_t n,
+    const uint8_t task_id[32], uint64_t now, uint64_t report_deadline, uint64_t task_expiration,
+    uint64_t report_expiry_age, const uint8_t* d_reports, uint32_t report_stride,
+    const uint32_t* d_report_len, uint8_t* d_report_ids, uint64_t* d_times,
+    uint8_t* d_public_shares, uint8_t* d_leader_input_shares, uint8_t* d_extensions,
+    uint32_t* d_ext_len, uint32_t ext_stride, uint8_t* d_helper_config_ids, uint8_t* d_helper_enc,
+    uint32_t helper_enc_len, uint8_t* d_helper_ct, uint32_t* d_helper_ct_len,
+    uint32_t helper_ct_stride, uint8_t* d_leader_config_ids, uint8_t* d_status, void* stream);
+int prio3_leader_upload_batch(
+    prio3_engine* engine, struct janus_hpke_opener* task_opener, uint8_t task_config_id,
+    struct janus_hpke_opener* global_opener, uint8_t global_config_id, uint32_t n,
+    const uint8_t task_id[32], uint64_t now, uint64_t report_deadline, uint64_t task_expiration,
+    uint64_t report_expiry_age, const uint8_t* reports, uint32_t report_stride,
+    const uint32_t* report_len, uint8_t* report_ids, uint64_t* times, uint8_t* public_shares,
+    uint8_t* leader_input_shares, uint8_t* extensions, uint32_t* ext_len, uint32_t ext_stride,
+    uint8_t* helper_config_ids, uint8_t* helper_enc, uint32_t helper_enc_len, uint8_t* helper_ct,
+    uint32_t* helper_ct_len, uint32_t helper_ct_stride, uint8_t* leader_config_ids,
+    uint8_t* status);
+
 /* ---- Client ---- */
 /* The client role of prio::vdaf: Prio3::shard on the caller's measurements (client/src/lib.rs:
  * 339-341).  Per report r: d_measurements[r][SumVec: length, else 1] (u64), d_nonces[r][16] (the

@@ -19,6 +19,9 @@
 //                 leader: AggregationJobResp into prepare messages and per-report errors; one
 //                 workgroup indexes the three regular record shapes speculatively, then the
 //                 parallel passes compare report IDs and gather the messages.
+//  k_rep_write    client: one Report row per report from the SoA buffers and the sealer's rows.
+//  k_rep_decode   leader upload: the inverse, one wave per Report row -- the field offsets and
+//                 lengths, the small fields, the helper's ciphertext rows and a malformed flag.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -1414,6 +1417,181 @@ int64_t janus_dap_report_encode_host(uint32_t n, const uint8_t* ids, const uint6
     emitted++;
   }
   return emitted;
+}
+
+}  // extern "C"
+
+// ---- leader side: Report decode ---------------------------------------------------------------
+namespace {
+// Walks one Report of `len` bytes: f[] = the JANUS_DAP_REPORT_* offsets and lengths, cfg[] = the two
+// config IDs.  The cursor o never passes len and every read is below it; false = does not decode.
+__host__ __device__ inline bool rep_parse(const uint8_t* row, uint32_t len, uint32_t* f,
+                                          uint32_t* cfg) {
+  if (len < 28) return false;
+  const uint32_t psl = ((uint32_t)row[24] << 24) | ((uint32_t)row[25] << 16) |
+                       ((uint32_t)row[26] << 8) | row[27];
+  uint32_t o = 28;
+  if (psl > len - o) return false;
+  f[0] = o;
+  f[1] = psl;
+  o += psl;
+  for (int c = 0; c < 2; c++) {
+    if (len - o < 3) return false;
+    cfg[c] = row[o];
+    const uint32_t el = ((uint32_t)row[o + 1] << 8) | row[o + 2];
+    o += 3;
+    if (el > len - o) return false;
+    f[2 + 4 * c] = o;
+    f[3 + 4 * c] = el;
+    o += el;
+    if (len - o < 4) return false;
+    const uint32_t pl = ((uint32_t)row[o] << 24) | ((uint32_t)row[o + 1] << 16) |
+                        ((uint32_t)row[o + 2] << 8) | row[o + 3];
+    o += 4;
+    if (pl > len - o) return false;
+    f[4 + 4 * c] = o;
+    f[5 + 4 * c] = pl;
+    o += pl;
+  }
+  return o == len;  // Report::get_decoded refuses trailing bytes
+}
+
+struct RdecArgs {
+  uint32_t n, stride, enc_len, ct_stride;
+  const uint8_t* rows;
+  const uint32_t* len;
+  uint8_t *ids, *lcfg, *hcfg, *henc, *hct, *bad;
+  uint64_t* times;
+  uint32_t *fields, *hct_len;
+};
+
+// k_rep_decode: one wave per report.  Every lane walks the (at most five) length prefixes itself --
+// the addresses are wave-uniform, so each is one broadcast load -- then the lanes share the small
+// outputs and copy the helper's ciphertext rows.  The leader's fields stay in the row: the upload
+// call reads them in place through fields[].
+__global__ __launch_bounds__(256) void k_rep_decode(RdecArgs a) {
+  const uint64_t r = 4ull * blockIdx.x + (threadIdx.x >> 6);
+  const uint32_t l = threadIdx.x & 63u;
+  if (r >= a.n) return;
+  const uint8_t* row = a.rows + (size_t)a.stride * r;
+  const uint32_t len = a.len[r];
+  uint32_t f[JANUS_DAP_REPORT_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, cfg[2] = {0, 0};
+  const bool ok = len <= a.stride && rep_parse(row, len, f, cfg);
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < JANUS_DAP_REPORT_FIELDS; i++) f[i] = 0;
+    cfg[0] = cfg[1] = 0;
+  }
+  const bool hok = ok && f[7] == a.enc_len && f[9] <= a.ct_stride;
+  if (l < 16) a.ids[16 * r + l] = ok ? row[l] : (uint8_t)0;
+  if (l == 16) {
+    uint64_t t = 0;
+    if (ok)
+      for (int i = 0; i < 8; i++) t = (t << 8) | row[16 + i];
+    a.times[r] = t;
+  }
+  if (l == 17) {
+#pragma unroll
+    for (int i = 0; i < JANUS_DAP_REPORT_FIELDS; i++) a.fields[JANUS_DAP_REPORT_FIELDS * r + i] = f[i];
+  }
+  if (l == 18) {
+    a.lcfg[r] = (uint8_t)cfg[0];
+    a.hcfg[r] = (uint8_t)cfg[1];
+    a.bad[r] = ok ? 0 : 1;
+    a.hct_len[r] = hok ? f[9] : 0u;
+  }
+  for (uint32_t k = l; k < a.enc_len; k += 64)
+    a.henc[(size_t)a.enc_len * r + k] = hok ? row[f[6] + k] : (uint8_t)0;  // f[6] + k < len
+  for (uint32_t k = l; k < a.ct_stride; k += 64)
+    a.hct[(size_t)a.ct_stride * r + k] = hok && k < f[9] ? row[f[8] + k] : (uint8_t)0;
+}
+
+bool rdec_args_ok(uint32_t n, const void* rows, uint32_t stride, const void* len, const void* ids,
+                  const void* times, const void* fields, const void* lcfg, const void* hcfg,
+                  const void* henc, uint32_t enc_len, const void* hct, const void* hct_len,
+                  uint32_t ct_stride, const void* bad) {
+  if (enc_len > 0xFFFF || stride >= (1u << 31)) return false;
+  if (n == 0) return true;
+  return len && ids && times && fields && lcfg && hcfg && hct_len && bad && (!stride || rows) &&
+         (!enc_len || henc) && (!ct_stride || hct);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t janus_dap_report_decode_host(uint32_t n, const uint8_t* reports, uint32_t stride,
+                                     const uint32_t* report_len, uint8_t* ids, uint64_t* times,
+                                     uint32_t* fields, uint8_t* lcfg, uint8_t* hcfg, uint8_t* henc,
+                                     uint32_t enc_len, uint8_t* hct, uint32_t* hct_len,
+                                     uint32_t ct_stride, uint8_t* bad) {
+  if (!rdec_args_ok(n, reports, stride, report_len, ids, times, fields, lcfg, hcfg, henc, enc_len,
+                    hct, hct_len, ct_stride, bad))
+    return JANUS_DAP_EARG;
+  int64_t decoded = 0;
+  for (uint32_t r = 0; r < n; r++) {
+    const uint8_t* row = reports + (size_t)stride * r;
+    uint32_t f[JANUS_DAP_REPORT_FIELDS] = {0}, cfg[2] = {0, 0};
+    const bool ok = report_len[r] <= stride && rep_parse(row, report_len[r], f, cfg);
+    if (!ok) {
+      memset(f, 0, sizeof f);
+      cfg[0] = cfg[1] = 0;
+    }
+    const bool hok = ok && f[7] == enc_len && f[9] <= ct_stride;
+    memset(ids + 16 * (size_t)r, 0, 16);
+    times[r] = 0;
+    if (ok) {
+      memcpy(ids + 16 * (size_t)r, row, 16);
+      for (int i = 0; i < 8; i++) times[r] = (times[r] << 8) | row[16 + i];
+    }
+    memcpy(fields + (size_t)JANUS_DAP_REPORT_FIELDS * r, f, sizeof f);
+    lcfg[r] = (uint8_t)cfg[0];
+    hcfg[r] = (uint8_t)cfg[1];
+    bad[r] = ok ? 0 : 1;
+    hct_len[r] = hok ? f[9] : 0u;
+    if (enc_len) memset(henc + (size_t)enc_len * r, 0, enc_len);
+    if (ct_stride) memset(hct + (size_t)ct_stride * r, 0, ct_stride);
+    if (hok) {
+      if (enc_len) memcpy(henc + (size_t)enc_len * r, row + f[6], enc_len);
+      if (f[9]) memcpy(hct + (size_t)ct_stride * r, row + f[8], f[9]);
+    }
+    decoded += ok;
+  }
+  return decoded;
+}
+
+int janus_dap_report_decode_device(uint32_t n, const uint8_t* d_reports, uint32_t stride,
+                                   const uint32_t* d_report_len, uint8_t* d_ids, uint64_t* d_times,
+                                   uint32_t* d_fields, uint8_t* d_lcfg, uint8_t* d_hcfg,
+                                   uint8_t* d_henc, uint32_t enc_len, uint8_t* d_hct,
+                                   uint32_t* d_hct_len, uint32_t ct_stride, uint8_t* d_bad,
+                                   void* stream) {
+  if (!rdec_args_ok(n, d_reports, stride, d_report_len, d_ids, d_times, d_fields, d_lcfg, d_hcfg,
+                    d_henc, enc_len, d_hct, d_hct_len, ct_stride, d_bad))
+    return JANUS_DAP_EARG;
+  if (n == 0) return 0;
+  const int dev = device_of(d_bad);
+  if (dev < 0) return JANUS_DAP_EARG;
+  DeviceGuard guard(dev);
+  DCHK(guard.rc);
+  RdecArgs a{};
+  a.n = n;
+  a.stride = stride;
+  a.enc_len = enc_len;
+  a.ct_stride = ct_stride;
+  a.rows = d_reports;
+  a.len = d_report_len;
+  a.ids = d_ids;
+  a.lcfg = d_lcfg;
+  a.hcfg = d_hcfg;
+  a.henc = d_henc;
+  a.hct = d_hct;
+  a.bad = d_bad;
+  a.times = d_times;
+  a.fields = d_fields;
+  a.hct_len = d_hct_len;
+  k_rep_decode<<<(uint32_t)(((uint64_t)n + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
+  DCHK(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

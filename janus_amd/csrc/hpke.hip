@@ -119,7 +119,8 @@ __device__ __noinline__ bool p384_dh(const int8_t* dig, const uint8_t* enc, uint
 }
 
 // MODE 0: explicit AAD, plaintext out.  MODE 1: DAP helper input share with PUB bytes of
-// public share (InputShareAad built here), decoded helper share out.
+// public share (InputShareAad built here), decoded helper share out.  MODE 2: Decap and the key
+// schedule only (the AEAD key and base nonce out; the leader upload's wide AEAD follows).
 // AEAD (P.aead): 1 AES-128-GCM, 2 AES-256-GCM, 3 ChaCha20Poly1305 (RFC 9180 7.3 ids).
 // KEM: 0x20 DHKEM(X25519, HKDF-SHA256) (enc: 32 bytes), 0x10 DHKEM(P-256, HKDF-SHA256) (enc: the
 // 65-byte uncompressed point), 0x21 DHKEM(X448, HKDF-SHA512) (56 bytes), 0x12 DHKEM(P-521,
@@ -274,6 +275,17 @@ __global__ __launch_bounds__(256) HPKE_WAVES void k_hpke_open(HpkeParams P, Open
     key_schedule_sha512<NSS, true>(P, KEM, ss, keyw, noncew);
   else
     key_schedule_sha512<NSS, false>(P, KEM, ss, keyw, noncew);
+  if constexpr (MODE == 2) {
+    // stage A of the leader upload's wide open (prio3_upload.hip): Decap and the key schedule only;
+    // a.pt holds 12 words per report -- the AEAD key (8 BE words), base_nonce (3), the KEM's verdict
+    uint32_t* ko = (uint32_t*)a.pt + 12 * (size_t)r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) ko[i] = keyw[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) ko[8 + i] = noncew[i];
+    ko[11] = ok ? 1u : 0u;
+    return;
+  }
   uint32_t aad_len, pt_len;
   uint8_t* pp;
   auto gcm_open = [&](auto nr_tag) {  // NR = 10 (AES-128-GCM) or 14 (AES-256-GCM)
@@ -944,7 +956,9 @@ static int launch_open(janus_hpke_opener* o, int mode, int pub, const OpenArgs& 
   }
   const uint32_t blocks = (a.n + 255) / 256;
 #define JANUS_HPKE_LAUNCH(KE)                                    \
-  if (mode == 0)                                                 \
+  if (mode == 2)                                                 \
+    k_hpke_open<2, 0, KE><<<blocks, 256, 0, st>>>(o->P, a);      \
+  else if (mode == 0)                                            \
     k_hpke_open<0, 0, KE><<<blocks, 256, 0, st>>>(o->P, a);      \
   else if (pub == 64)                                            \
     k_hpke_open<1, 64, KE><<<blocks, 256, 0, st>>>(o->P, a);     \
@@ -1028,6 +1042,45 @@ int hpke_open_group_launch(janus_hpke_opener* o, const HpkeGroupArgs& g, hipStre
   a.n_idx = g.n_idx;
   std::lock_guard<std::mutex> lk(o->mu);  // o->P and the timing list
   return launch_open(o, 1, (int)g.pub_len, a, st) == JANUS_HPKE_SUCCESS ? PRIO3_OK : PRIO3_EDEVICE;
+}
+
+// ---- leader upload hooks (prio3_upload.hip) ----
+uint32_t hpke_opener_aead(const janus_hpke_opener* o) { return o->P.aead; }
+
+// Decap and key schedule alone for the reports idx[0 .. *n_idx) (k_hpke_open MODE 2): keys[r][12]
+int hpke_upload_keys_launch(janus_hpke_opener* o, uint32_t n, const uint8_t* enc, uint32_t* keys,
+                            const uint32_t* idx, const uint32_t* n_idx, hipStream_t st) {
+  OpenArgs a{};
+  a.n = n;
+  a.enc = enc;
+  a.pt = (uint8_t*)keys;
+  a.idx = idx;
+  a.n_idx = n_idx;
+  std::lock_guard<std::mutex> lk(o->mu);  // o->P and the timing list
+  return launch_open(o, 2, 0, a, st) == JANUS_HPKE_SUCCESS ? PRIO3_OK : PRIO3_EDEVICE;
+}
+
+// The whole one-lane open with explicit AAD rows (MODE 0) for the reports idx[0 .. *n_idx)
+int hpke_upload_open_launch(janus_hpke_opener* o, uint32_t n, const uint8_t* enc, const uint8_t* ct,
+                            const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* aad,
+                            const uint32_t* aad_len, uint32_t aad_stride, uint8_t* pt,
+                            uint8_t* status, const uint32_t* idx, const uint32_t* n_idx,
+                            hipStream_t st) {
+  OpenArgs a{};
+  a.n = n;
+  a.ct_stride = ct_stride;
+  a.aad_stride = aad_stride;
+  a.enc = enc;
+  a.ct = ct;
+  a.ct_len = ct_len;
+  a.aad = aad;
+  a.aad_len = aad_len;
+  a.pt = pt;
+  a.status = status;
+  a.idx = idx;
+  a.n_idx = n_idx;
+  std::lock_guard<std::mutex> lk(o->mu);
+  return launch_open(o, 0, 0, a, st) == JANUS_HPKE_SUCCESS ? PRIO3_OK : PRIO3_EDEVICE;
 }
 
 uint64_t hpke_group_key(const HpkeJob* j) {

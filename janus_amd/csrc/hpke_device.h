@@ -9,6 +9,7 @@
 #include "prio3_device.h"
 #include "sha256_device.h"
 #include "sha512_device.h"
+#include "ghash_device.h"
 
 // -------------------------------------------------------------------------------------
 // GF(2^255 - 19), values in [0, 2^256) (loosely reduced), 8 little-endian 32-bit limbs
@@ -485,30 +486,6 @@ DEV fe x25519_ladder_pair(const uint32_t* k, const fe& u, const bool odd) {
   fe_cswap(swap, x2, x3);
   fe_cswap(swap, z2, z3);
   return fe_freeze(fe_mul(x2, fe_inv(z2)));
-}
-
-// GHASH step (SP 800-38D Algorithm 1): y = (y ^ x) * H in GF(2^128), big-endian words
-DEV void ghash_block(uint32_t y[4], const uint32_t x[4], const uint32_t H[4]) {
-  uint32_t X[4] = {y[0] ^ x[0], y[1] ^ x[1], y[2] ^ x[2], y[3] ^ x[3]};
-  uint32_t Z[4] = {0, 0, 0, 0}, V[4] = {H[0], H[1], H[2], H[3]};
-#pragma unroll
-  for (int wi = 0; wi < 4; wi++) {
-#pragma unroll 8
-    for (int bit = 31; bit >= 0; bit--) {
-      const uint32_t m = 0u - ((X[wi] >> bit) & 1u);
-      Z[0] ^= V[0] & m;
-      Z[1] ^= V[1] & m;
-      Z[2] ^= V[2] & m;
-      Z[3] ^= V[3] & m;
-      const uint32_t lsb = 0u - (V[3] & 1u);
-      V[3] = __builtin_amdgcn_alignbit(V[2], V[3], 1);
-      V[2] = __builtin_amdgcn_alignbit(V[1], V[2], 1);
-      V[1] = __builtin_amdgcn_alignbit(V[0], V[1], 1);
-      V[0] = (V[0] >> 1) ^ (0xe1000000u & lsb);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) y[i] = Z[i];
 }
 
 // -------------------------------------------------------------------------------------

@@ -677,6 +677,9 @@ struct prio3_engine {
   // option: a released run's slab stays in the GPU's pool even above the pool's budget (a
   // device-resident caller running FPVec batches back to back; default: the budget applies)
   int keep_scratch = 0;
+  // option: the AEAD of the leader upload's open (prio3_upload.hip) -- 0 by payload length, 1 the
+  // one-lane body of k_hpke_open, 2 k_aead_open_wide (AES-GCM; ChaCha20Poly1305 is always 1)
+  int upload_aead = 0;
   Mp64Params mp{};  // PRIO3_SUMVEC_F64_MP only
   uint64_t* d_sigma64 = nullptr;
   uint4* d_sigma128 = nullptr;  // k_query_w's sigma table (DevParams::sigma_dev)

@@ -1380,7 +1380,7 @@ int prio3_engine_set_option(prio3_engine* e, const char* key, int64_t value) {
               {"coalesce", &e->coalesce},          {"experimental_fpvec", &e->experimental_fpvec},
               {"leader_fuse_acc", &e->leader_fuse_acc},
               {"force_generic_query", &e->force_generic}, {"pair_max", &e->pair_max},
-              {"keep_scratch", &e->keep_scratch}};
+              {"keep_scratch", &e->keep_scratch},  {"upload_aead", &e->upload_aead}};
   for (auto& o : ints)
     if (!strcmp(key, o.name)) {
       *o.field = (int)value;

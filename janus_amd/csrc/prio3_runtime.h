@@ -402,6 +402,17 @@ struct HpkeGroupArgs {
 };
 int hpke_open_group_launch(janus_hpke_opener* o, const HpkeGroupArgs& a, hipStream_t st);
 int hpke_opener_device(const janus_hpke_opener* o);
+// the leader upload (prio3_upload.hip): the opener's AEAD id; Decap + key schedule alone into
+// keys[r][12] (key: 8 BE words, base nonce: 3, the KEM's verdict); the whole one-lane open with
+// explicit AAD rows -- both over the reports idx[0 .. *n_idx) (device memory), grid over n
+uint32_t hpke_opener_aead(const janus_hpke_opener* o);
+int hpke_upload_keys_launch(janus_hpke_opener* o, uint32_t n, const uint8_t* enc, uint32_t* keys,
+                            const uint32_t* idx, const uint32_t* n_idx, hipStream_t st);
+int hpke_upload_open_launch(janus_hpke_opener* o, uint32_t n, const uint8_t* enc, const uint8_t* ct,
+                            const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* aad,
+                            const uint32_t* aad_len, uint32_t aad_stride, uint8_t* pt,
+                            uint8_t* status, const uint32_t* idx, const uint32_t* n_idx,
+                            hipStream_t st);
 uint64_t hpke_group_key(const HpkeJob* j);
 void hpke_layout(const HpkeJob* j, uint32_t cap, HpkeLayout* L);
 // the group's inputs to a device mirror (one DMA per field), the open kernel, outputs back

@@ -21,6 +21,8 @@ DAP_EXPORTED_SYMBOLS = (
     "janus_dap_agg_job_resp_unpack_device",
     # client side
     "janus_dap_report_max_len", "janus_dap_report_encode_device", "janus_dap_report_encode_host",
+    # leader upload
+    "janus_dap_report_decode_host", "janus_dap_report_decode_device",
 )
 NO_ERROR = 0xFF  # prepare_error value meaning "no DAP-level error for this report"
 
@@ -73,6 +75,10 @@ def _lib():
         L.janus_dap_report_encode_host.argtypes = rep
         L.janus_dap_report_encode_host.restype = C.c_int64
         L.janus_dap_report_encode_device.argtypes = rep + [vp]
+        dec = [u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp]
+        L.janus_dap_report_decode_host.argtypes = dec
+        L.janus_dap_report_decode_host.restype = C.c_int64
+        L.janus_dap_report_decode_device.argtypes = dec + [vp]
         _bound = True
     return L
 
@@ -513,3 +519,83 @@ def report_encode_device(report_ids, times, public_shares, leader_config_id: int
     if rc:
         raise RuntimeError(f"janus_dap_report_encode_device failed (rc={rc})")
     return out, out_len
+
+
+# ---- leader upload: the Report rows, decoded -------------------------------------------------
+REPORT_FIELDS = 10  # JANUS_DAP_REPORT_FIELDS
+(F_PUBLIC_SHARE_OFF, F_PUBLIC_SHARE_LEN, F_LEADER_ENC_OFF, F_LEADER_ENC_LEN, F_LEADER_PAYLOAD_OFF,
+ F_LEADER_PAYLOAD_LEN, F_HELPER_ENC_OFF, F_HELPER_ENC_LEN, F_HELPER_PAYLOAD_OFF,
+ F_HELPER_PAYLOAD_LEN) = range(REPORT_FIELDS)
+
+
+def _decode_shapes(reports, report_len, helper_enc_len, helper_ct_stride):
+    if len(reports.shape) != 2 or tuple(report_len.shape) != (reports.shape[0],):
+        raise ValueError("reports must be [n, report_stride] and report_len [n]")
+    if not 0 <= int(helper_enc_len) <= 0xFFFF:
+        raise ValueError("helper_enc_len is u16-prefixed")
+    if reports.shape[1] >= 1 << 31 or not 0 <= int(helper_ct_stride) < 1 << 32:
+        raise ValueError("report_stride must be below 2^31 and helper_ct_stride fit a u32")
+    return reports.shape[0], reports.shape[1]
+
+
+def report_decode_host(reports, report_len, helper_enc_len: int, helper_ct_stride: int):
+    """The inverse of report_encode_host (janus_dap_report_decode_host, no GPU): reports uint8
+    [n, report_stride] with report_len [n] -> dict of report_ids [n, 16], times uint64 [n], fields
+    uint32 [n, REPORT_FIELDS] (offset and length of the public share and of both ciphertexts' enc
+    and payload within the row, at the F_* indices), leader_config_ids, helper_config_ids, the
+    helper ciphertext rows helper_enc [n, helper_enc_len] / helper_ct [n, helper_ct_stride] /
+    helper_ct_len [n], and malformed uint8 [n] (1: the Report does not decode; its outputs are
+    zero)."""
+    rows = np.ascontiguousarray(reports, np.uint8)
+    ln = np.ascontiguousarray(report_len, np.uint32)
+    n, stride = _decode_shapes(rows, ln, helper_enc_len, helper_ct_stride)
+    out = dict(report_ids=np.empty((n, 16), np.uint8), times=np.empty(n, np.uint64),
+               fields=np.empty((n, REPORT_FIELDS), np.uint32),
+               leader_config_ids=np.empty(n, np.uint8), helper_config_ids=np.empty(n, np.uint8),
+               helper_enc=np.empty((n, helper_enc_len), np.uint8),
+               helper_ct=np.empty((n, helper_ct_stride), np.uint8),
+               helper_ct_len=np.empty(n, np.uint32), malformed=np.empty(n, np.uint8))
+    w = lambda a: _np_ptr(a) if a.size else None  # noqa: E731
+    rc = _lib().janus_dap_report_decode_host(
+        n, w(rows), stride, _np_ptr(ln), _np_ptr(out["report_ids"]), _np_ptr(out["times"]),
+        _np_ptr(out["fields"]), _np_ptr(out["leader_config_ids"]),
+        _np_ptr(out["helper_config_ids"]), w(out["helper_enc"]), helper_enc_len,
+        w(out["helper_ct"]), _np_ptr(out["helper_ct_len"]), helper_ct_stride,
+        _np_ptr(out["malformed"]))
+    if rc < 0:
+        raise ValueError(f"janus_dap_report_decode_host failed (rc={rc})")
+    return out
+
+
+def report_decode_device(reports, report_len, helper_enc_len: int, helper_ct_stride: int,
+                         stream=None):
+    """Device form on torch tensors of one GPU (reports uint8 [n, report_stride], report_len int32
+    [n], as prepare_reports_device returns them): the same dict as report_decode_host, as tensors
+    (times int64, fields / helper_ct_len int32); no host synchronisation."""
+    import torch
+    dev = reports.device
+    if dev.type != "cuda":
+        raise ValueError("report_decode_device takes GPU tensors")
+    _dev_tensor("reports", reports, 1, dev)
+    _dev_tensor("report_len", report_len, 4, dev)
+    n, stride = _decode_shapes(reports, report_len, helper_enc_len, helper_ct_stride)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(report_ids=torch.empty((n, 16), **u8),
+               times=torch.empty(n, dtype=torch.int64, device=dev),
+               fields=torch.empty((n, REPORT_FIELDS), **i32),
+               leader_config_ids=torch.empty(n, **u8), helper_config_ids=torch.empty(n, **u8),
+               helper_enc=torch.empty((n, helper_enc_len), **u8),
+               helper_ct=torch.empty((n, helper_ct_stride), **u8),
+               helper_ct_len=torch.empty(n, **i32), malformed=torch.empty(n, **u8))
+    if n == 0:
+        return out
+    w = lambda t: _tptr(t) if t.numel() else None  # noqa: E731
+    rc = _lib().janus_dap_report_decode_device(
+        n, w(reports), stride, _tptr(report_len), _tptr(out["report_ids"]), _tptr(out["times"]),
+        _tptr(out["fields"]), _tptr(out["leader_config_ids"]), _tptr(out["helper_config_ids"]),
+        w(out["helper_enc"]), helper_enc_len, w(out["helper_ct"]), _tptr(out["helper_ct_len"]),
+        helper_ct_stride, _tptr(out["malformed"]), _stream(stream, dev.index or 0))
+    if rc:
+        raise RuntimeError(f"janus_dap_report_decode_device failed (rc={rc})")
+    return out

@@ -34,6 +34,11 @@ STATUS_FINISHED = 0
 STATUS_PREP_INIT = 1
 STATUS_PREP_SHARE_DECODE = 2
 STATUS_PREP_MSG = 3
+# leader upload (prio3_leader_upload_batch): per-report status, Janus's ReportRejectionReason from 1
+(UPLOAD_OK, UPLOAD_INTERVAL_COLLECTED, UPLOAD_DECRYPT_FAILURE, UPLOAD_DECODE_FAILURE,
+ UPLOAD_TASK_EXPIRED, UPLOAD_EXPIRED, UPLOAD_TOO_EARLY, UPLOAD_OUTDATED_HPKE_CONFIG) = range(8)
+UPLOAD_MALFORMED, UPLOAD_HOST = 0x40, 0x41
+UINT64_MAX = (1 << 64) - 1
 STATUS_PREP_NEXT = 4
 STATUS_PEER_MISMATCH = 5
 STATUS_INPUT_SHARE_DECODE = 6
@@ -110,6 +115,7 @@ EXPORTED_SYMBOLS = (
     "prio3_leader_prepare_next_aggregate_batch",
     "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
     "prio3_client_rand_len", "prio3_client_report_stride", "prio3_selftest_tile",
+    "prio3_device_leader_upload", "prio3_leader_upload_batch",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -205,6 +211,11 @@ def load_library() -> C.CDLL:
     L.prio3_client_prepare_reports_device.argtypes = [vp, vp, vp, u32, vp, C.c_uint64, vp, vp, vp,
                                                       vp, vp, vp, C.c_uint8, C.c_uint8, C.c_int,
                                                       vp, u32, vp, vp, vp]
+    u8, u64 = C.c_uint8, C.c_uint64
+    up = [vp, vp, u8, vp, u8, u32, vp, u64, u64, u64, u64, vp, u32, vp, vp, vp, vp, vp, vp, vp, u32,
+          vp, vp, u32, vp, vp, u32, vp, vp]
+    L.prio3_leader_upload_batch.argtypes = up
+    L.prio3_device_leader_upload.argtypes = up + [vp]
     _lib = L
     return L
 
@@ -934,6 +945,121 @@ class HelperEngine:
             _tptr(out["report_len"]), _tptr(out["status"]), _stream(stream, self.device))
         if rc:
             raise RuntimeError(f"prio3_client_prepare_reports_device failed (rc={rc})")
+        return out
+
+    # ---- leader upload ----------------------------------------------------------------
+    def _upload_args(self, task_opener, global_opener, task_config_id, global_config_id, task_id,
+                     report_stride, ext_stride):
+        if task_opener is None and global_opener is None:
+            raise ValueError("the upload needs the task's opener, the global one, or both")
+        for o in (task_opener, global_opener):
+            if o is not None and o.device != self.device:
+                raise ValueError("an opener is bound to another GPU than the engine")
+        if len(task_id) != 32:
+            raise ValueError("task_id must be 32 bytes")
+        if not 0 <= int(task_config_id) <= 0xFF or not 0 <= int(global_config_id) <= 0xFF:
+            raise ValueError("an HPKE config id is one byte")
+        if report_stride % 4 or ext_stride % 4 or ext_stride < 0:
+            raise ValueError("report_stride and ext_stride must be multiples of 4")
+        return (None if task_opener is None else task_opener.handle, int(task_config_id),
+                None if global_opener is None else global_opener.handle, int(global_config_id))
+
+    def leader_upload_batch(self, reports, report_len, task_id: bytes, now: int,
+                            report_deadline: int, task_opener=None, task_config_id: int = 0,
+                            global_opener=None, global_config_id: int = 0,
+                            task_expiration: int = UINT64_MAX, report_expiry_age: int = UINT64_MAX,
+                            ext_stride: int = 64, helper_enc_len: int = 32,
+                            helper_ct_stride: int = 0) -> dict:
+        """The leader's upload handler for a batch of one task (prio3_leader_upload_batch; host
+        buffers, blocking): reports uint8 [n, report_stride] with report_len [n] -> dict of
+        report_ids, times, public_shares, leader_input_shares, extensions / ext_len, the helper
+        ciphertext rows (helper_config_ids, helper_enc, helper_ct, helper_ct_len),
+        leader_config_ids and status (0, UPLOAD_* = Janus's ReportRejectionReason from 1,
+        UPLOAD_MALFORMED, UPLOAD_HOST).  Rows of a report with non-zero status are zero."""
+        rows = np.ascontiguousarray(reports, np.uint8)
+        ln = np.ascontiguousarray(report_len, np.uint32)
+        if rows.ndim != 2 or ln.shape != (rows.shape[0],):
+            raise ValueError("reports must be [n, report_stride] and report_len [n]")
+        n, stride = rows.shape
+        ho, hc, go, gc = self._upload_args(task_opener, global_opener, task_config_id,
+                                           global_config_id, task_id, stride, ext_stride)
+        sz = self.sz
+        out = dict(report_ids=np.zeros((n, 16), np.uint8), times=np.zeros(n, np.uint64),
+                   public_shares=np.zeros((n, sz.public_share_len), np.uint8),
+                   leader_input_shares=np.zeros((n, sz.leader_input_share_len), np.uint8),
+                   extensions=np.zeros((n, ext_stride), np.uint8), ext_len=np.zeros(n, np.uint32),
+                   helper_config_ids=np.zeros(n, np.uint8),
+                   helper_enc=np.zeros((n, helper_enc_len), np.uint8),
+                   helper_ct=np.zeros((n, helper_ct_stride), np.uint8),
+                   helper_ct_len=np.zeros(n, np.uint32), leader_config_ids=np.zeros(n, np.uint8),
+                   status=np.zeros(n, np.uint8))
+        w = lambda a: _np_ptr(a) if a.size else None  # noqa: E731
+        tid = (C.c_uint8 * 32).from_buffer_copy(bytes(task_id))
+        rc = load_library().prio3_leader_upload_batch(
+            self.handle, ho, hc, go, gc, n, tid, int(now), int(report_deadline),
+            int(task_expiration), int(report_expiry_age), w(rows), stride, _np_ptr(ln),
+            _np_ptr(out["report_ids"]), _np_ptr(out["times"]), w(out["public_shares"]),
+            _np_ptr(out["leader_input_shares"]), w(out["extensions"]), _np_ptr(out["ext_len"]),
+            ext_stride, _np_ptr(out["helper_config_ids"]), w(out["helper_enc"]), helper_enc_len,
+            w(out["helper_ct"]), _np_ptr(out["helper_ct_len"]), helper_ct_stride,
+            _np_ptr(out["leader_config_ids"]), _np_ptr(out["status"]))
+        if rc == -3:
+            raise NotImplementedError("prio3_leader_upload_batch: unsupported instance")
+        if rc:
+            raise RuntimeError(f"prio3_leader_upload_batch failed (rc={rc})")
+        return out
+
+    def leader_upload_device(self, reports, report_len, task_id: bytes, now: int,
+                             report_deadline: int, task_opener=None, task_config_id: int = 0,
+                             global_opener=None, global_config_id: int = 0,
+                             task_expiration: int = UINT64_MAX,
+                             report_expiry_age: int = UINT64_MAX, ext_stride: int = 64,
+                             helper_enc_len: int = 32, helper_ct_stride: int = 0,
+                             stream=None) -> dict:
+        """Device form (prio3_device_leader_upload) on torch tensors of the engine's GPU: reports
+        uint8 [n, report_stride], report_len int32 [n], as prepare_reports_device returns them.
+        Returns the same dict as leader_upload_batch, as tensors (times int64, the lengths int32);
+        no host synchronisation."""
+        import torch
+        for t, es in ((reports, 1), (report_len, 4)):
+            if not isinstance(t, torch.Tensor) or not t.is_contiguous() or \
+                    t.device.type != "cuda" or t.device.index != self.device or \
+                    t.element_size() != es:
+                raise ValueError("reports / report_len must be contiguous uint8 / 4-byte tensors "
+                                 "on the engine's GPU")
+        if reports.dim() != 2 or tuple(report_len.shape) != (reports.shape[0],):
+            raise ValueError("reports must be [n, report_stride] and report_len [n]")
+        n, stride = reports.shape
+        ho, hc, go, gc = self._upload_args(task_opener, global_opener, task_config_id,
+                                           global_config_id, task_id, stride, ext_stride)
+        sz = self.sz
+        dev = reports.device
+        u8 = dict(dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = dict(report_ids=torch.empty((n, 16), **u8),
+                   times=torch.empty(n, dtype=torch.int64, device=dev),
+                   public_shares=torch.empty((n, sz.public_share_len), **u8),
+                   leader_input_shares=torch.empty((n, sz.leader_input_share_len), **u8),
+                   extensions=torch.empty((n, ext_stride), **u8), ext_len=torch.empty(n, **i32),
+                   helper_config_ids=torch.empty(n, **u8),
+                   helper_enc=torch.empty((n, helper_enc_len), **u8),
+                   helper_ct=torch.empty((n, helper_ct_stride), **u8),
+                   helper_ct_len=torch.empty(n, **i32), leader_config_ids=torch.empty(n, **u8),
+                   status=torch.empty(n, **u8))
+        w = lambda t: _tptr(t) if t.numel() else None  # noqa: E731
+        tid = (C.c_uint8 * 32).from_buffer_copy(bytes(task_id))
+        rc = load_library().prio3_device_leader_upload(
+            self.handle, ho, hc, go, gc, n, tid, int(now), int(report_deadline),
+            int(task_expiration), int(report_expiry_age), w(reports), stride, _tptr(report_len),
+            _tptr(out["report_ids"]), _tptr(out["times"]), w(out["public_shares"]),
+            _tptr(out["leader_input_shares"]), w(out["extensions"]), _tptr(out["ext_len"]),
+            ext_stride, _tptr(out["helper_config_ids"]), w(out["helper_enc"]), helper_enc_len,
+            w(out["helper_ct"]), _tptr(out["helper_ct_len"]), helper_ct_stride,
+            _tptr(out["leader_config_ids"]), _tptr(out["status"]), _stream(stream, self.device))
+        if rc == -3:
+            raise NotImplementedError("prio3_device_leader_upload: unsupported instance")
+        if rc:
+            raise RuntimeError(f"prio3_device_leader_upload failed (rc={rc})")
         return out
 
     # ---- measurement ----------------------------------------------------------------
