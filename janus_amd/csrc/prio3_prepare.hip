@@ -1560,14 +1560,14 @@ __device__ __forceinline__ void query_h_body(const DevParams& p, const InPtrs& i
   uint8_t status = LEADER ? out.status[r] : PRIO3_STATUS_FINISHED;  // leader: unpack verdict
   uint8_t* lout = LEADER ? out.prep_msgs + (size_t)r * p.prep_share_len : nullptr;
   const T t = ldf<F>(sc.qr, 0, ld, r);
-  T L0, sumL = F::zero();
+  T sumL = F::zero();
   // u_e = t^e / P.  PP <= 16: one in-register DFT.  PP == 32: decimation in frequency,
   // X[2k] = DFT16(u_e + u_(e+16)), X[2k+1] = DFT16((u_e - u_(e+16)) w32^e), each a geometric
   // sequence, so only 16 values (64 VGPRs) are live at a time.
   auto store_L = [&](int idx, const T& val) {  // X[idx] = L_c with c = (P - idx) mod P
     const uint32_t c = (uint32_t)((PP - idx) & (PP - 1));
     if (c == 0) {
-      L0 = val;
+      F::store(sc.Lbuf, r, val);  // row 0: L_0, read back with each sweep's finish operands
     } else if (c <= K) {
       F::store(sc.Lbuf, (size_t)c * ld + r, val);
       sumL = F::add(sumL, val);
@@ -1658,6 +1658,10 @@ __device__ __forceinline__ void query_h_body(const DevParams& p, const InPtrs& i
     }
     range = mac_reduce_f(R);
   }
+  // p(t), the range sum and (below) L/2 are not needed inside the wire sweeps: they wait in this
+  // lane's column of PVbuf (unused on this path) instead of in registers the sweeps are short of
+  F::store(sc.PVbuf, (size_t)1 * ld + r, pt);
+  F::store(sc.PVbuf, (size_t)2 * ld + r, range);
   const T r0 = ldf<F>(sc.jr, 0, ld, r);
   {
     // r0^C by square-and-multiply over the (uniform) bits of C
@@ -1682,7 +1686,7 @@ __device__ __forceinline__ void query_h_body(const DevParams& p, const InPtrs& i
     }
   }
   const T half = FC<F>::half(p);
-  const T halfL = F::mul(half, sumL);
+  F::store(sc.PVbuf, r, F::mul(half, sumL));
   const uint8_t* lps = in.leader + (size_t)r * p.prep_share_len;
   bool decode_ok = true;
   auto lv = [&](uint32_t e) {
@@ -1693,49 +1697,127 @@ __device__ __forceinline__ void query_h_body(const DevParams& p, const InPtrs& i
   sum128 Ssum;
   sum_zero(Ssum);
   T G = F::zero(), rj = r0;
+  uint64_t lane = (uint64_t)sc.meas + (uint64_t)r * F::ES;  // see ldrow below
+  asm("" : "+v"(lane));
   for (uint32_t jg = 0; jg < C; jg += GS) {
     mac128 Aa[GS], Bb[GS];
-    T mc[GS];
 #pragma unroll
     for (int q = 0; q < GS; q++) {
       mac_zero(Aa[q]);
       mac_zero(Bb[q]);
     }
-    // One dwordx4 load per element from a clamped (always in-bounds) address; padding
-    // elements are zeroed with a wave-uniform mask (a select on the loaded value made the
-    // compiler split the load into four branch-guarded dword loads).
-    auto fetch = [&](uint32_t k, T* dst) {
+    // The operands of one gadget call: its GS measurement elements, beta_k and L_(k+1), each one
+    // dwordx4 load from a clamped (always in-bounds) address.  Padding elements are zeroed at
+    // their use with a wave-uniform mask (a select on the loaded value made the compiler split
+    // the load into four branch-guarded dword loads).
+    //
+    // A call's operands are issued WIRE_AHEAD trips before the trip that multiplies by them:
+    // the rows come from L2 misses, and one trip's arithmetic (64 v_mad_u64_u32) is what hides
+    // the round trip.  Written as "load the next call's into temporaries, copy at the end of the
+    // trip", the compiler moved the beta / L loads across the back edge to the top of the trip
+    // that consumes them (only the measurement elements stayed a trip ahead).  So the loop is
+    // unrolled over WIRE_AHEAD + 1 register sets with no copy between them, and use() opens with
+    // a compiler-level barrier that neither the loads above it nor the multiplies below it can
+    // cross (tools/isa_load_use.py reads the result off the assembly).  Two trips ahead also
+    // fits the registers and measured slower (profiles/r09/SUMMARY.txt).
+    constexpr int WIRE_AHEAD = 1;
+    struct wire_ops {
+      T m[GS];
+      T be, L;
+    };
+    // Row e of scratch array X for this lane is read at lane + ((X - meas) + e * ld * ES): one
+    // 64-bit lane address for all six arrays of the sweep, the bracket wave-uniform (SGPRs).
+    // Left to itself the compiler keeps a lane address pair per array live through the sweep,
+    // which the second register set has no room for.  The lane address is opaque and the
+    // offset goes through readfirstlane so that the sum is not split up and hoisted again.
+    auto ldrow = [&](const void* base, uint32_t e) {
+      const uint64_t off = ((uint64_t)base - (uint64_t)sc.meas) + (uint64_t)e * ld * F::ES;
+      const uint64_t offu =
+          ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(off >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off);
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)(lane + offu);  // global
+      return mk128(v.x, v.y, v.z, v.w);
+    };
+    const uint32_t Klast = K ? K - 1 : 0;
+    auto issue = [&](uint32_t k, wire_ops& s) {
 #pragma unroll
       for (int q = 0; q < GS; q++) {
         const uint32_t i = k * C + jg + q;
         const bool valid = (k < K) && (jg + q < C) && (i < M);
-        const uint32_t msk = valid ? 0xffffffffu : 0u;
-        const uint4 v = ((const uint4*)sc.meas)[(size_t)(valid ? i : 0) * ld + r];
-        dst[q] = mk128(v.x & msk, v.y & msk, v.z & msk, v.w & msk);
+        s.m[q] = ldrow(sc.meas, i & (valid ? 0xffffffffu : 0u));  // a mask, not a branch
       }
+      const uint32_t kc = min(k, Klast);
+      s.be = ldrow(sc.beta, kc);
+      s.L = ldrow(sc.Lbuf, kc + 1);
     };
-    fetch(0, mc);
-    // The per-call coefficients beta_k, L_(k+1) of the next call are loaded together with its
-    // measurement elements, one iteration ahead (they come from L2/MALL, and loading them at
-    // their use left the waves parked on s_waitcnt).
-    T be = ldf<F>(sc.beta, 0, ld, r), Lk = ldf<F>(sc.Lbuf, 1, ld, r);
-#pragma unroll 1
-    for (uint32_t k = 0; k < K; k++) {
-      T mn[GS];
-      fetch(k + 1, mn);
-      const uint32_t kn = k + 1 < K ? k + 1 : k;
-      const T be_n = ldf<F>(sc.beta, kn, ld, r), L_n = ldf<F>(sc.Lbuf, kn + 1, ld, r);
+    auto use = [&](uint32_t k, wire_ops& s) {  // k < K
+      // the barrier: the loads issued before it stay above it, and this call's multiplies,
+      // which all read m[q], stay below it
+#pragma unroll
+      for (int q = 0; q < GS; q++)
+        asm volatile(""
+                     : "+v"(s.m[q].w[0]), "+v"(s.m[q].w[1]), "+v"(s.m[q].w[2]), "+v"(s.m[q].w[3])
+                     :
+                     : "memory");
 #pragma unroll
       for (int q = 0; q < GS; q++) {
-        mac_add(Aa[q], be, mc[q]);
-        mac_add(Bb[q], Lk, mc[q]);
-        sum_add(Ssum, mc[q]);
+        const bool valid = (jg + q < C) && (k * C + jg + q < M);
+        const uint32_t msk = valid ? 0xffffffffu : 0u;
+        const T mc = mk128(s.m[q].w[0] & msk, s.m[q].w[1] & msk, s.m[q].w[2] & msk,
+                           s.m[q].w[3] & msk);
+        mac_add(Aa[q], s.be, mc);
+        mac_add(Bb[q], s.L, mc);
+        sum_add(Ssum, mc);
       }
+    };
+    constexpr int NS = WIRE_AHEAD + 1;
+    wire_ops ws[NS];
+    // (opaque, so that the row offsets of these first loads are formed here and not kept in
+    // SGPRs across all sweeps, which spilled them)
+    uint32_t k = __builtin_amdgcn_readfirstlane(0);
+    asm volatile("" : "+s"(k));
 #pragma unroll
-      for (int q = 0; q < GS; q++) mc[q] = mn[q];
-      be = be_n;
-      Lk = L_n;
+    for (int u = 0; u < WIRE_AHEAD; u++) issue(k + u, ws[u]);
+    // K mod NS leading trips (these copy between the sets), then whole rounds of NS trips
+#pragma unroll 1
+    for (uint32_t e = K % NS; e; e--, k++) {
+      issue(k + WIRE_AHEAD, ws[WIRE_AHEAD]);
+      use(k, ws[0]);
+#pragma unroll
+      for (int u = 0; u < WIRE_AHEAD; u++) ws[u] = ws[u + 1];
     }
+#pragma unroll 1
+    for (; k < K; k += NS) {
+#pragma unroll
+      for (int u = 0; u < NS; u++) {
+        issue(k + u + WIRE_AHEAD, ws[(u + WIRE_AHEAD) % NS]);
+        use(k + u, ws[u]);
+      }
+    }
+    // The sweep's finish operands -- L_0, r, the two proof seeds of each wire and, for the
+    // helper, its two leader verifier elements -- go into the registers the loop has just freed,
+    // in two batches: what the first reduction needs right after the last trip, the rest behind
+    // that reduction, which frees an accumulator and hides their round trip.  One exposed wait
+    // per sweep instead of three per wire.  An idle second wire (j >= C) loads the first wire's
+    // operands again and does not use them.
+    T sd[2 * GS], lw[2 * GS], r0f;
+    auto fin_load = [&](int q) {
+      const uint32_t jc = jg + q < C ? jg + q : jg;
+      if constexpr (!LEADER) {
+        lw[2 * q] = F::load(lps, 1 + 2 * jc);
+        lw[2 * q + 1] = F::load(lps, 2 + 2 * jc);
+      }
+    };
+    const T L0 = ldrow(sc.Lbuf, 0), halfL = ldrow(sc.PVbuf, 0);
+#pragma unroll
+    for (int q = 0; q < GS; q++) {
+      const uint32_t jc = jg + q < C ? jg + q : jg;
+      sd[2 * q + 1] = ldrow(sc.proofs, 2 * jc + 1);
+      sd[2 * q] = ldrow(sc.proofs, 2 * jc);
+    }
+    fin_load(0);
+    asm volatile("" ::: "memory");
     // Wire values at t, lazily reduced: f1 = seed_(2j+1) L0 + B_j - L/2 folds the seed term into
     // B's accumulator, f0 = seed_2j L0 + r^(j+1) A_j is one two-product MAC, and the gadget
     // products of the group are summed in one MAC before a single reduction.
@@ -1744,27 +1826,38 @@ __device__ __forceinline__ void query_h_body(const DevParams& p, const InPtrs& i
 #pragma unroll
     for (int q = 0; q < GS; q++) {
       const uint32_t j = jg + q;
-      if (j < C) {  // wave-uniform
-        mac_add(Bb[q], ldf<F>(sc.proofs, 2 * j + 1, ld, r), L0);
-        const T f1 = F::sub(mac_reduce_f(Bb[q]), halfL);
+      if (q == 0 || j < C) {  // wave-uniform; the first wire of a sweep always exists
+        mac_add(Bb[q], sd[2 * q + 1], L0);
+        T f1 = F::sub(mac_reduce_f(Bb[q]), halfL);
+        if (q == 0) {
+          // second batch, kept behind the first reduction by the barrier on its result
+          asm volatile("" : "+v"(f1.w[0])::"memory");
+          r0f = ldrow(sc.jr, 0);
+#pragma unroll
+          for (int q2 = 1; q2 < GS; q2++) fin_load(q2);
+          asm volatile("" ::: "memory");
+        }
         const T Aq = mac_reduce_f(Aa[q]);
         mac128 F0;
         mac_zero(F0);
-        mac_add(F0, ldf<F>(sc.proofs, 2 * j, ld, r), L0);
+        mac_add(F0, sd[2 * q], L0);
         mac_add(F0, rj, Aq);
         const T f0 = mac_reduce_f(F0);
         if constexpr (LEADER) {
           F::store(lout, 1 + 2 * j, f0);
           F::store(lout, 2 + 2 * j, f1);
         } else {
-          mac_add(Gq, F::add(lv(1 + 2 * j), f0), F::add(lv(2 + 2 * j), f1));
+          if (!F::lt_p(lw[2 * q]) || !F::lt_p(lw[2 * q + 1])) decode_ok = false;
+          mac_add(Gq, F::add(lw[2 * q], f0), F::add(lw[2 * q + 1], f1));
         }
-        rj = F::mul(rj, r0);
+        rj = F::mul(rj, r0f);
       }
     }
     if constexpr (!LEADER) G = F::add(G, mac_reduce_f(Gq));
   }
   const T S = sum_reduce(Ssum);
+  pt = ldf<F>(sc.PVbuf, 1, ld, r);
+  range = ldf<F>(sc.PVbuf, 2, ld, r);
   T v;
   if (p.kind == PRIO3_SUMVEC) {
     v = range;
