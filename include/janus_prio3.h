@@ -321,6 +321,65 @@ int prio3_batch_metadata(prio3_engine* engine, uint32_t n, const uint8_t* report
                          const uint64_t* times, const uint8_t* status, const uint8_t* accept_mask,
                          const uint32_t* segment_ids, uint32_t n_segments, uint8_t* checksums_out,
                          uint64_t* intervals_out);
+/* ---- Job index ---- */
+/* The per-report bookkeeping that tells the accumulate which report goes where and which reports
+ * may be counted, from the d_report_ids[n][16] and d_times[n] that janus_dap_agg_init_unpack_device
+ * and prio3_device_leader_upload write, to the d_segment_ids / d_accept_mask the prepare, finish,
+ * accumulate and metadata calls above read:
+ *  - Batch identifier (TimeInterval::to_batch_identifier, aggregator_core/src/query_type.rs:72-82;
+ *    Time::to_batch_interval_start, core/src/time.rs:207-224): start = t - t % time_precision.
+ *    Segment s is the s-th distinct start in ASCENDING order (what numpy.unique(...,
+ *    return_inverse=True) gives; the writer's by_batch_identifier_index,
+ *    aggregation_job_writer.rs:598), written to d_segment_starts[s]; rows >= n_segments are zero.
+ *    A report whose start + time_precision overflows a u64 (Interval::new fails) takes no segment:
+ *    d_segment_ids = 0xFFFFFFFF, d_accept_mask = 0, counted in n_time_errors.
+ *    time_precision == 0 is a fixed-size task: every report is in segment 0, n_segments = 1 when
+ *    n > 0, d_segment_starts is not written and the closed intervals are not read.
+ *  - Overflow: more than max_segments (1..4096) distinct starts give overflow = 1 and n_segments =
+ *    max_segments + 1; the caller discards the job's other outputs.  They stay safe for the calls
+ *    queued behind this one: every d_segment_ids[i] is then 0xFFFFFFFF with d_accept_mask[i] = 0
+ *    and d_reject[i] = 0, d_segment_starts is zero and n_closed is 0 (n_time_errors, d_duplicate and
+ *    the duplicate counts are what they are without overflow).  A caller that does not synchronise
+ *    passes max_segments as n_segments to the later calls: empty segments come back with count 0,
+ *    checksum 0 and Interval::EMPTY.
+ *  - Closed batches (fail_report_aggregations_for_collected_batches, aggregation_job_writer.rs:
+ *    540-588): closed_intervals is a HOST array [k][2] = (start, duration), k <= 1024 (NULL when
+ *    k = 0), read before the call returns.  A segment is closed when its start lies in
+ *    [start_j, start_j + duration_j) for some j (no wrap-around: an end past 2^64 - 1 closes
+ *    every later start); the decision is made once per segment.  Its reports get d_accept_mask = 0
+ *    and d_reject = PRIO3_REJECT_BATCH_COLLECTED (0x80 | PrepareError::BatchCollected, the
+ *    convention of prio3_helper_aggregate_init_batch) and are counted in n_closed; every other
+ *    report with a segment gets d_accept_mask = 1, and d_reject = 0 in any case.
+ *  - Duplicate report IDs (the HashSet over every PrepareInit, aggregator.rs:1765-1773):
+ *    d_duplicate[i] = 1 exactly when some j < i has the same 16 bytes (copies at 3, 7 and 9 mark 7
+ *    and 9; first_duplicate = 7).  Nothing is rejected for it -- the reference fails the whole
+ *    request, which stays the caller's decision -- and d_accept_mask does not depend on it.
+ * Two runs over the same inputs give byte-identical outputs.  d_segment_starts, d_reject and
+ * d_duplicate may each be NULL.  n == 0 succeeds with an all-zero info except first_duplicate.
+ * PRIO3_EINVAL: n > 2^30, max_segments 0 or above 4096, k > 1024, a missing buffer.
+ * Device form: stream-ordered, no host synchronisation, scratch from the GPU's pool (8 n to 16 n
+ * bytes for the ID table); d_report_ids 16-byte aligned.  Host form: a plain blocking call. */
+enum { PRIO3_REJECT_BATCH_COLLECTED = 0x80 };
+typedef struct {
+  uint32_t n_segments;      /* distinct batch identifiers found, if <= max_segments */
+  uint32_t overflow;        /* 1: more than max_segments distinct identifiers */
+  uint32_t n_duplicates;    /* reports whose ID also occurs at a lower index */
+  uint32_t first_duplicate; /* lowest such index; 0xFFFFFFFF if none */
+  uint32_t n_closed;        /* reports in a closed batch */
+  uint32_t n_time_errors;   /* reports whose batch interval overflows u64 */
+} prio3_job_index_info;
+int prio3_device_job_index(prio3_engine* engine, uint32_t n, const uint8_t* d_report_ids,
+                           const uint64_t* d_times, uint64_t time_precision,
+                           const uint64_t* closed_intervals, uint32_t k, uint32_t max_segments,
+                           uint32_t* d_segment_ids, uint64_t* d_segment_starts,
+                           uint8_t* d_accept_mask, uint8_t* d_reject, uint8_t* d_duplicate,
+                           prio3_job_index_info* d_info, void* stream);
+int prio3_job_index(prio3_engine* engine, uint32_t n, const uint8_t* report_ids,
+                    const uint64_t* times, uint64_t time_precision,
+                    const uint64_t* closed_intervals, uint32_t k, uint32_t max_segments,
+                    uint32_t* segment_ids, uint64_t* segment_starts, uint8_t* accept_mask,
+                    uint8_t* reject, uint8_t* duplicate, prio3_job_index_info* info);
+
 /* Copies the output shares of the last device prepare (n x agg_share_len) to host. */
 int prio3_device_output_shares(prio3_engine* engine, uint32_t n, uint8_t* out);
 

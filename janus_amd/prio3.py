@@ -96,6 +96,15 @@ class Prio3Sizes(C.Structure):
         "agg_share_len", "leader_input_share_len")]
 
 
+class Prio3JobIndexInfo(C.Structure):
+    """prio3_job_index_info (include/janus_prio3.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_segments", "overflow", "n_duplicates",
+                                          "first_duplicate", "n_closed", "n_time_errors")]
+
+
+#: d_reject of a report in a closed batch: 0x80 | PrepareError::BatchCollected
+REJECT_BATCH_COLLECTED = 0x80
+
 #: Every symbol include/janus_prio3.h declares.
 EXPORTED_SYMBOLS = (
     "prio3_sizes", "prio3_engine_create", "prio3_engine_destroy", "prio3_helper_prepare_batch",
@@ -116,6 +125,7 @@ EXPORTED_SYMBOLS = (
     "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
     "prio3_client_rand_len", "prio3_client_report_stride", "prio3_selftest_tile",
     "prio3_device_leader_upload", "prio3_leader_upload_batch",
+    "prio3_device_job_index", "prio3_job_index",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -204,6 +214,9 @@ def load_library() -> C.CDLL:
                                               vp, vp]
     L.prio3_batch_metadata.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
     L.prio3_device_combine_metadata.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    jix = [vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    L.prio3_device_job_index.argtypes = jix + [vp, vp]
+    L.prio3_job_index.argtypes = jix + [P(Prio3JobIndexInfo)]
     L.prio3_client_rand_len.argtypes = [P(Prio3Params)]
     L.prio3_client_shard_device.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.prio3_client_shard_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
@@ -734,6 +747,62 @@ class HelperEngine:
         if rc:
             raise RuntimeError(f"prio3_batch_metadata failed (rc={rc})")
         return ck, iv
+
+    @staticmethod
+    def _closed(closed_intervals):
+        """[k, 2] uint64 (start, duration) host array of the closed batch intervals, or None."""
+        if closed_intervals is None:
+            return None, 0
+        c = np.ascontiguousarray(closed_intervals, np.uint64).reshape(-1, 2)
+        return (c, c.shape[0]) if c.shape[0] else (None, 0)
+
+    def job_index_device(self, report_ids, times, time_precision: int, max_segments: int,
+                         segment_ids, accept_mask, info, closed_intervals=None,
+                         segment_starts=None, reject=None, duplicate=None, stream=None) -> None:
+        """prio3_device_job_index on torch tensors of this engine's GPU: report_ids [n, 16] uint8
+        and times [n] (64-bit; None for time_precision 0) in; segment_ids [n] (32-bit), accept_mask
+        [n] uint8, info [6] (32-bit: the fields of Prio3JobIndexInfo in order) and the optional
+        segment_starts [max_segments] (64-bit), reject [n] and duplicate [n] uint8 out.
+        closed_intervals is a host array [k, 2] of (start, duration).  Stream-ordered; nothing is
+        waited for."""
+        c, k = self._closed(closed_intervals)
+        rc = load_library().prio3_device_job_index(
+            self.handle, report_ids.shape[0], _tptr(report_ids), _tptr(times), time_precision,
+            _np_ptr(c), k, max_segments, _tptr(segment_ids), _tptr(segment_starts),
+            _tptr(accept_mask), _tptr(reject), _tptr(duplicate), _tptr(info),
+            _stream(stream, self.device))
+        if rc:
+            raise RuntimeError(f"prio3_device_job_index failed (rc={rc})")
+
+    def job_index(self, report_ids, times, time_precision: int, max_segments: int,
+                  closed_intervals=None, with_starts: bool = True, with_reject: bool = True,
+                  with_duplicate: bool = True) -> dict:
+        """Host-buffer form (blocking): returns segment_ids, segment_starts, accept_mask, reject,
+        duplicate (None for an output switched off; segment_starts also for time_precision 0) and
+        the fields of Prio3JobIndexInfo."""
+        ids = np.ascontiguousarray(report_ids, np.uint8).reshape(-1, 16)
+        n = ids.shape[0]
+        t = None if times is None else np.ascontiguousarray(times, np.uint64)
+        if t is not None and t.shape != (n,):
+            raise ValueError(f"times must have shape ({n},), got {t.shape}")
+        c, k = self._closed(closed_intervals)
+        seg = np.zeros(n, np.uint32)
+        acc = np.zeros(n, np.uint8)
+        cap = max(0, min(int(max_segments), 4096))
+        starts = np.zeros(cap, np.uint64) if with_starts and time_precision else None
+        rej = np.zeros(n, np.uint8) if with_reject else None
+        dup = np.zeros(n, np.uint8) if with_duplicate else None
+        info = Prio3JobIndexInfo()
+        rc = load_library().prio3_job_index(
+            self.handle, n, _np_ptr(ids), _np_ptr(t), time_precision, _np_ptr(c), k, max_segments,
+            _np_ptr(seg), _np_ptr(starts), _np_ptr(acc), _np_ptr(rej), _np_ptr(dup),
+            C.byref(info))
+        if rc:
+            raise RuntimeError(f"prio3_job_index failed (rc={rc})")
+        out = dict(segment_ids=seg, segment_starts=starts, accept_mask=acc, reject=rej,
+                   duplicate=dup)
+        out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
+        return out
 
     def device_output_shares(self, n: int) -> np.ndarray:
         out = np.zeros((n, self.sz.agg_share_len), np.uint8)
