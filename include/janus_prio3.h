@@ -510,25 +510,32 @@ int prio3_leader_upload_batch(
 
 /* ---- Client ---- */
 /* The client role of prio::vdaf: Prio3::shard on the caller's measurements (client/src/lib.rs:
- * 339-341).  Per report r: d_measurements[r][SumVec: length, else 1] (u64), d_nonces[r][16] (the
- * report ID) and d_rand[r][prio3_client_rand_len] from the caller's CSPRNG (the library draws no
- * randomness, and a row must never be reused).  Randomness layout, prio's order, 16-byte seeds:
+ * 339-341), for Count, Sum, SumVec, Histogram and SumVecField64MultiproofHmacSha256Aes128
+ * (PRIO3_SUMVEC_F64_MP).  Per report r: d_measurements[r][SumVec and the multiproof SumVec:
+ * length, else 1] (u64), d_nonces[r][16] (the report ID) and d_rand[r][prio3_client_rand_len] from
+ * the caller's CSPRNG (the library draws no randomness, and a row must never be reused).
+ * Randomness layout, prio's order, seeds of the instance's XOF seed size -- 16 bytes
+ * (XofTurboShake128), 32 bytes for PRIO3_SUMVEC_F64_MP (XofHmacSha256Aes128: 160 bytes per report):
  *   helper measurement share seed | helper proofs share seed |
  *   [ helper blind | leader blind | ]  prove randomness seed
- * -- the two blinds only for instances with joint randomness (Sum, SumVec, Histogram: joint_rand_len
- * of prio3_sizes non-zero); without them (Count) the prove seed follows the two helper seeds.
+ * -- the two blinds only for instances with joint randomness (Sum, SumVec, the multiproof SumVec,
+ * Histogram: joint_rand_len of prio3_sizes non-zero); without them (Count) the prove seed follows
+ * the two helper seeds.
  * Outputs per report: d_public_shares[r][public_share_len] (may be NULL when that is 0),
  * d_leader_input_shares[r][leader_input_share_len], d_helper_shares[r][helper_share_len] and
  * d_status[r]: PRIO3_CLIENT_OK, or PRIO3_CLIENT_INVALID_MEASUREMENT for a measurement prio's
- * encode_measurement rejects (Count: not 0 / 1; Sum, SumVec: an entry >= 2^bits; Histogram: an
- * index >= length) -- its three rows are all zero and the other reports are not affected.
+ * encode_measurement rejects (Count: not 0 / 1; Sum, SumVec, the multiproof SumVec: an entry
+ * >= 2^bits; Histogram: an index >= length) -- its three rows are all zero and the other reports
+ * are not affected.  The multiproof instance's leader input share holds the measurement share, then
+ * all num_proofs proof shares (little-endian Field64), then the 32-byte leader blind; its public
+ * share is the two 32-byte joint-rand parts, the leader's first.
  * Every XOF expansion is sampled exactly (rejection sampling as prio does; there is no "unusable"
  * flag as in the synthetic generator below), the engine's verify key is not read, and nothing of
  * the leader's prepare_init is computed.  Device pointers are 16-byte aligned.  Stream-ordered;
  * the call does not wait for the device.
- * PRIO3_SUMVEC_F64_MP and PRIO3_FPVEC_BOUNDED_L2 return PRIO3_EUNSUPPORTED from every entry point
- * of this section (FPVec's circuit is a reconstruction and its fixed-point encoding needs a
- * contract of its own); their seeded generators below stay. */
+ * PRIO3_FPVEC_BOUNDED_L2 returns PRIO3_EUNSUPPORTED from every entry point of this section (its
+ * circuit is a reconstruction and its fixed-point encoding needs a contract of its own); its
+ * seeded generator below stays. */
 enum { PRIO3_CLIENT_OK = 0, PRIO3_CLIENT_INVALID_MEASUREMENT = 1 };
 /* seed_size * (5 with joint randomness, else 3); 0 for parameters prio3_sizes rejects */
 int prio3_client_rand_len(const prio3_params* params);

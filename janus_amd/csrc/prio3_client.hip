@@ -406,9 +406,9 @@ __global__ __launch_bounds__(64) void k_gen(DevParams p, uint64_t seed, uint64_t
 // rejection sampler bx_expand (as k_slow_redo does for the helper).
 // ====================================================================================
 struct ShardIn {
-  const uint64_t* meas;  // [n][SumVec: length, else 1]
+  const uint64_t* meas;  // [n][SumVec (Field128 or multiproof Field64): length, else 1]
   const uint8_t* nonces;  // [n][16]
-  const uint8_t* rand;    // [n][16 * (5 with joint randomness, else 3)]
+  const uint8_t* rand;    // [n][seed size (16; multiproof: 32) * (5 with joint randomness, else 3)]
 };
 struct ShardOut {
   uint8_t *pub, *leader, *helper, *status;
@@ -987,38 +987,21 @@ DEV void mp_expand(const AesT& A, const Mp64Params& P, const uint32_t seed[8], i
   (void)expand_soa(A, s, base, ld, r, n);
 }
 
-__global__ __launch_bounds__(64) void k_gen_mp64(DevParams p, Mp64Params P, uint64_t seed,
-                                                 uint64_t first, GenScratch gs, GenOut go,
-                                                 uint8_t* lin, uint64_t invP, uint64_t inv2P) {
-  __shared__ AesT A;
-  aes_tables_init(A);
-  __syncthreads();
+// Prio3::shard of one report after its measurement's encoding (gs.meas, column r): the helper
+// measurement share's expansion and the leader's lm = meas - hm (left in gs.lm), both joint-rand
+// parts and the seed, joint and prove randomness, the num_proofs proofs (proof k: prove rand rows
+// k A .., joint rand row k), the helper proofs share, and the report's three output rows.  Every
+// expansion is sampled exactly (expand_soa).  Shared by the seeded generator and the client role.
+DEV void mp_shard_lane(const AesT& A, const DevParams& p, const Mp64Params& P, const GenScratch& gs,
+                       uint32_t r, const uint32_t nonce[4], const uint32_t k_hm[8],
+                       const uint32_t k_hp[8], const uint32_t k_hb[8], const uint32_t k_lb[8],
+                       const uint32_t k_pr[8], uint8_t* leader_row, uint8_t* helper_row,
+                       uint8_t* pub_row, uint64_t invP, uint64_t inv2P) {
   typedef Fp64 F;
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= p.n) return;
   const size_t ld = p.ld;
   // DevParams::proof_len counts every proof here; Mp64Params::proof_len is one proof's
-  const uint32_t M = p.meas_len, np = P.np, Ar = p.arity, PL = P.proof_len, Ln = p.length;
-  GenStream gst;
-  gen_stream_init(gst.st, seed, first + r);
-  uint32_t nonce[4], k_hm[8], k_hp[8], k_hb[8], k_lb[8], k_pr[8];
-  // stream words in increasing order (GenStream moves forward only; words 42, 43 of the last
-  // seed are in the second block)
-  for (int k = 0; k < 4; k++) nonce[k] = gst.word(k);
-  for (int k = 0; k < 8; k++) k_hm[k] = gst.word(4 + k);
-  for (int k = 0; k < 8; k++) k_hp[k] = gst.word(12 + k);
-  for (int k = 0; k < 8; k++) k_hb[k] = gst.word(20 + k);
-  for (int k = 0; k < 8; k++) k_lb[k] = gst.word(28 + k);
-  for (int k = 0; k < 8; k++) k_pr[k] = gst.word(36 + k);
-  uint64_t* meas = (uint64_t*)gs.meas;
-  const uint64_t mask = p.bits < 64 ? (1ull << p.bits) - 1 : ~0ull;
-  for (uint32_t e = 0; e < Ln; e++) {
-    uint64_t v = (uint64_t)gst.word(44 + 2 * e);
-    v |= (uint64_t)gst.word(45 + 2 * e) << 32;
-    v &= mask;
-    if (go.meas) go.meas[(size_t)r * Ln + e] = v;
-    for (uint32_t b = 0; b < p.bits; b++) meas[(size_t)(e * p.bits + b) * ld + r] = (v >> b) & 1;
-  }
+  const uint32_t M = p.meas_len, np = P.np, Ar = p.arity, PL = P.proof_len;
+  const uint64_t* meas = (const uint64_t*)gs.meas;
   // shares and joint-rand parts
   uint64_t* hm = (uint64_t*)gs.hm;
   uint64_t* lm = (uint64_t*)gs.lm;
@@ -1052,17 +1035,16 @@ __global__ __launch_bounds__(64) void k_gen_mp64(DevParams p, Mp64Params P, uint
   // leader input share = enc(lm) || enc(proofs - helper proofs share) || k_blind
   uint64_t* hp = (uint64_t*)gs.hp;
   mp_expand(A, P, k_hp, 2, bnp, 2, hp, ld, r, PL * np);
-  uint64_t* li = (uint64_t*)(lin + (size_t)r * p.leader_share_len);
+  uint64_t* li = (uint64_t*)leader_row;
   for (uint32_t i = 0; i < M; i++) li[i] = lm[(size_t)i * ld + r];
   const uint64_t* prf = (const uint64_t*)gs.proof;
   for (uint32_t i = 0; i < PL * np; i++)
     li[M + i] = F::sub(prf[(size_t)i * ld + r], hp[(size_t)i * ld + r]);
   uint32_t* lt = (uint32_t*)(li + M + PL * np);
   for (int k = 0; k < 8; k++) lt[k] = k_lb[k];
-  // public outputs
-  *(uint4*)(go.nonces + 16 * (size_t)r) = make_uint4(nonce[0], nonce[1], nonce[2], nonce[3]);
-  uint32_t* hs = (uint32_t*)(go.helper + (size_t)r * p.helper_share_len);
-  uint32_t* pb = (uint32_t*)(go.pub + (size_t)r * p.public_share_len);
+  // helper input share = the three helper seeds; public share = both joint-rand parts
+  uint32_t* hs = (uint32_t*)helper_row;
+  uint32_t* pb = (uint32_t*)pub_row;
   for (int k = 0; k < 8; k++) {
     hs[k] = k_hm[k];
     hs[8 + k] = k_hp[k];
@@ -1070,7 +1052,45 @@ __global__ __launch_bounds__(64) void k_gen_mp64(DevParams p, Mp64Params P, uint
     pb[k] = part0[k];
     pb[8 + k] = part1[k];
   }
+}
+
+__global__ __launch_bounds__(64) void k_gen_mp64(DevParams p, Mp64Params P, uint64_t seed,
+                                                 uint64_t first, GenScratch gs, GenOut go,
+                                                 uint8_t* lin, uint64_t invP, uint64_t inv2P) {
+  __shared__ AesT A;
+  aes_tables_init(A);
+  __syncthreads();
+  typedef Fp64 F;
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  const size_t ld = p.ld;
+  const uint32_t Ln = p.length;
+  GenStream gst;
+  gen_stream_init(gst.st, seed, first + r);
+  uint32_t nonce[4], k_hm[8], k_hp[8], k_hb[8], k_lb[8], k_pr[8];
+  // stream words in increasing order (GenStream moves forward only; words 42, 43 of the last
+  // seed are in the second block)
+  for (int k = 0; k < 4; k++) nonce[k] = gst.word(k);
+  for (int k = 0; k < 8; k++) k_hm[k] = gst.word(4 + k);
+  for (int k = 0; k < 8; k++) k_hp[k] = gst.word(12 + k);
+  for (int k = 0; k < 8; k++) k_hb[k] = gst.word(20 + k);
+  for (int k = 0; k < 8; k++) k_lb[k] = gst.word(28 + k);
+  for (int k = 0; k < 8; k++) k_pr[k] = gst.word(36 + k);
+  uint64_t* meas = (uint64_t*)gs.meas;
+  const uint64_t mask = p.bits < 64 ? (1ull << p.bits) - 1 : ~0ull;
+  for (uint32_t e = 0; e < Ln; e++) {
+    uint64_t v = (uint64_t)gst.word(44 + 2 * e);
+    v |= (uint64_t)gst.word(45 + 2 * e) << 32;
+    v &= mask;
+    if (go.meas) go.meas[(size_t)r * Ln + e] = v;
+    for (uint32_t b = 0; b < p.bits; b++) meas[(size_t)(e * p.bits + b) * ld + r] = (v >> b) & 1;
+  }
+  mp_shard_lane(A, p, P, gs, r, nonce, k_hm, k_hp, k_hb, k_lb, k_pr,
+                lin + (size_t)r * p.leader_share_len, go.helper + (size_t)r * p.helper_share_len,
+                go.pub + (size_t)r * p.public_share_len, invP, inv2P);
+  *(uint4*)(go.nonces + 16 * (size_t)r) = make_uint4(nonce[0], nonce[1], nonce[2], nonce[3]);
   if (go.leader_out) {  // truncate(lm): entry e = sum_b 2^b lm[e bits + b]
+    const uint64_t* lm = (const uint64_t*)gs.lm;
     uint64_t* lo = (uint64_t*)(go.leader_out + (size_t)r * p.out_len * 8);
     for (uint32_t e = 0; e < p.out_len; e++) {
       uint64_t acc = 0, pw = 1;
@@ -1082,6 +1102,53 @@ __global__ __launch_bounds__(64) void k_gen_mp64(DevParams p, Mp64Params P, uint
     }
   }
   if (go.flags) go.flags[r] = 0;
+}
+
+// The client role for this instance (prio3_client_shard_device): Prio3::shard on the caller's
+// measurements, nonces and randomness (five 32-byte seeds: helper measurement share, helper
+// proofs share, helper blind, leader blind, prove randomness), one report per lane.  An entry
+// >= 2^bits (SumVec::encode_measurement's check) gives PRIO3_CLIENT_INVALID_MEASUREMENT and three
+// all-zero rows.  No verify key, nothing of the leader's prepare_init, and no redo launch: the
+// expansions reject in line.
+__global__ __launch_bounds__(64) void k_shard_mp64(DevParams p, Mp64Params P, GenScratch gs,
+                                                   ShardIn in, ShardOut out, uint64_t invP,
+                                                   uint64_t inv2P) {
+  __shared__ AesT A;
+  aes_tables_init(A);
+  __syncthreads();
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  const size_t ld = p.ld;
+  const uint32_t Ln = p.length, nb = p.bits;
+  uint8_t* li = out.leader + (size_t)r * p.leader_share_len;
+  uint8_t* hs = out.helper + (size_t)r * p.helper_share_len;
+  uint8_t* pb = out.pub + (size_t)r * p.public_share_len;
+  // encode_measurement: the entries' bits into gs.meas, validated on the way
+  uint64_t* meas = (uint64_t*)gs.meas;
+  bool valid = true;
+  for (uint32_t e = 0; e < Ln; e++) {
+    const uint64_t v = in.meas[(size_t)r * Ln + e];
+    valid = valid && (nb >= 64 || (v >> nb) == 0);
+    for (uint32_t b = 0; b < nb; b++) meas[(size_t)(e * nb + b) * ld + r] = (v >> b) & 1;
+  }
+  if (!valid) {  // all three rows zero (every row length is a multiple of 8)
+    for (uint32_t k = 0; k < p.leader_share_len / 8; k++) ((uint64_t*)li)[k] = 0;
+    for (uint32_t k = 0; k < p.helper_share_len / 8; k++) ((uint64_t*)hs)[k] = 0;
+    for (uint32_t k = 0; k < p.public_share_len / 8; k++) ((uint64_t*)pb)[k] = 0;
+    out.status[r] = PRIO3_CLIENT_INVALID_MEASUREMENT;
+    return;
+  }
+  uint32_t nonce[4], k_hm[8], k_hp[8], k_hb[8], k_lb[8], k_pr[8];
+  load16(in.nonces + 16 * (size_t)r, nonce);
+  const uint8_t* rnd = in.rand + (size_t)r * 160;
+  uint32_t* const seeds[5] = {k_hm, k_hp, k_hb, k_lb, k_pr};
+#pragma unroll
+  for (int s = 0; s < 5; s++) {
+    load16(rnd + 32 * s, seeds[s]);
+    load16(rnd + 32 * s + 16, seeds[s] + 4);
+  }
+  mp_shard_lane(A, p, P, gs, r, nonce, k_hm, k_hp, k_hb, k_lb, k_pr, li, hs, pb, invP, inv2P);
+  out.status[r] = PRIO3_CLIENT_OK;
 }
 
 // ====================================================================================
@@ -1525,17 +1592,20 @@ static int gen_mp64(prio3_engine* e, uint32_t n, uint64_t seed, uint64_t first_i
 
 // The SoA scratch of k_gen and k_shard: slots[i] is the GenScratch member buffer i backs and
 // counts[i] its elements per report.  The first GEN_SHARD_BUFS are the client's shard (k_shard
-// takes only those); the rest belong to the generator's leader prepare_init.
+// and k_shard_mp64 take only those); the rest belong to the generator's leader prepare_init.
+// The multiproof instance holds every proof's prove and joint randomness (DevParams::proof_len
+// already counts every proof).
 constexpr size_t GEN_SCRATCH_BUFS = 15, GEN_SHARD_BUFS = 11;
 static void gen_scratch_carve(const DevParams& p, GenScratch& gs, void** slots[GEN_SCRATCH_BUFS],
                               size_t counts[GEN_SCRATCH_BUFS]) {
   const size_t A = p.arity, P = p.P;
+  const size_t np = p.kind == PRIO3_SUMVEC_F64_MP ? p.proof_len / (p.arity + p.glen) : 1;
   void** s[GEN_SCRATCH_BUFS] = {&gs.meas, &gs.hm, &gs.lm, &gs.wires, &gs.evals, &gs.g, &gs.tmp,
                                 &gs.proof, &gs.hp, &gs.prand, &gs.jr, &gs.qr, &gs.L, &gs.PV,
                                 &gs.acc};
   const size_t c[GEN_SCRATCH_BUFS] = {p.meas_len, p.meas_len, p.meas_len, A * P, A * 2 * P, 2 * P,
-                                      2 * P, p.proof_len, p.proof_len, A,
-                                      p.jr_len ? p.jr_len : 1, 1, P, P, A};
+                                      2 * P, p.proof_len, p.proof_len, A * np,
+                                      (p.jr_len ? p.jr_len : 1) * np, 1, P, P, A};
   for (size_t i = 0; i < GEN_SCRATCH_BUFS; i++) {
     slots[i] = s[i];
     counts[i] = c[i];
@@ -1625,7 +1695,16 @@ done:
 // Client role (janus_prio3.h, "Client"): k_shard on pooled scratch, and the one call that chains
 // it with the two seals and the Report encode.
 // ====================================================================================
-static bool client_takes(const prio3_engine* e) { return e->dp.kind <= PRIO3_HISTOGRAM; }
+static bool client_takes(const prio3_engine* e) {
+  return e->dp.kind <= PRIO3_HISTOGRAM || e->dp.kind == PRIO3_SUMVEC_F64_MP;
+}
+// u64 values per report of the measurement array, and bytes per report of the randomness
+static uint32_t client_meas_stride(const DevParams& p) {
+  return p.kind == PRIO3_SUMVEC || p.kind == PRIO3_SUMVEC_F64_MP ? p.length : 1;
+}
+static uint32_t client_rand_stride(const DevParams& p) {
+  return (p.kind == PRIO3_SUMVEC_F64_MP ? 32u : 16u) * (p.jr_len ? 5 : 3);
+}
 
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1640,9 +1719,10 @@ static size_t shard_scratch_per_report(const DevParams& p) {
 }
 
 // k_shard over the m <= ld reports at `in` / `out` (ld % 64 == 0), or with redo the one deferred
-// k_shard_redo over all m reports (any m), on the scratch at base
-static int shard_launch(DevParams p, uint32_t m, uint32_t ld, uint8_t* base, const ShardIn& in,
-                        const ShardOut& out, bool redo, hipStream_t st) {
+// k_shard_redo over all m reports (any m), on the scratch at base.  The multiproof instance (mp
+// its constants) is k_shard_mp64, which rejects in line: its redo is no launch.
+static int shard_launch(DevParams p, const Mp64Params& mp, uint32_t m, uint32_t ld, uint8_t* base,
+                        const ShardIn& in, const ShardOut& out, bool redo, hipStream_t st) {
   GenScratch gs{};
   void** slots[GEN_SCRATCH_BUFS];
   size_t counts[GEN_SCRATCH_BUFS];
@@ -1654,7 +1734,10 @@ static int shard_launch(DevParams p, uint32_t m, uint32_t ld, uint8_t* base, con
   p.n = m;
   p.ld = ld;
   const uint32_t blocks = ((redo ? ld : m) + 63) / 64;
-  if (p.es == 16) {
+  if (p.kind == PRIO3_SUMVEC_F64_MP) {
+    const uint64_t ip = (uint64_t)hpow(p.P, HP64 - 2, HP64), i2 = (uint64_t)hpow(2 * p.P, HP64 - 2, HP64);
+    if (!redo) k_shard_mp64<<<blocks, 64, 0, st>>>(p, mp, gs, in, out, ip, i2);
+  } else if (p.es == 16) {
     const f128 ip = h128x(hpow(p.P, HP128 - 2, HP128)), i2 = h128x(hpow(2 * p.P, HP128 - 2, HP128));
     if (redo)
       k_shard_redo<Fp128><<<blocks, 64, 0, st>>>(p, gs, in, out, ip, i2);
@@ -1710,20 +1793,19 @@ extern "C" int prio3_client_shard_device(prio3_engine* e, uint32_t n,
   int rc = PRIO3_OK;
   Slab* slab = acquire_chunked(e->device, per, chunk, st, &rc);
   if (!slab) return rc;
-  const uint32_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1;
-  const uint32_t rl = p.jr_len ? 80 : 48;
+  const uint32_t mstride = client_meas_stride(p), rl = client_rand_stride(p);
   for (uint64_t off = 0; off < n && rc == PRIO3_OK; off += chunk) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
     ShardIn in{d_measurements + (size_t)mstride * off, d_nonces + 16 * off, d_rand + (size_t)rl * off};
     ShardOut out{d_public_shares ? d_public_shares + (size_t)p.public_share_len * off : nullptr,
                  d_leader_input_shares + (size_t)p.leader_share_len * off,
                  d_helper_shares + (size_t)p.helper_share_len * off, d_status + off};
-    rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, false, st);
+    rc = shard_launch(p, e->mp, m, (uint32_t)chunk, slab->base, in, out, false, st);
   }
   if (rc == PRIO3_OK) {  // the reports that met a rejection, all chunks' in one launch
     ShardIn in{d_measurements, d_nonces, d_rand};
     ShardOut out{d_public_shares, d_leader_input_shares, d_helper_shares, d_status};
-    rc = shard_launch(p, n, (uint32_t)chunk, slab->base, in, out, true, st);
+    rc = shard_launch(p, e->mp, n, (uint32_t)chunk, slab->base, in, out, true, st);
   }
   ws_release(slab, st);
   return rc;
@@ -1744,7 +1826,7 @@ extern "C" int prio3_client_shard_batch(prio3_engine* e, uint32_t n, const uint6
   if (dg_.rc != hipSuccess) return PRIO3_EDEVICE;
   hipStream_t st = ws_stream_get(e->device);
   if (!st) return PRIO3_EDEVICE;
-  const size_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1, rl = p.jr_len ? 80 : 48;
+  const size_t mstride = client_meas_stride(p), rl = client_rand_stride(p);
   const size_t sizes[7] = {8 * mstride * n, 16 * (size_t)n, rl * n, (size_t)p.public_share_len * n,
                            (size_t)p.leader_share_len * n, (size_t)p.helper_share_len * n, n};
   size_t offs[8] = {0};
@@ -1856,16 +1938,15 @@ extern "C" int prio3_client_prepare_reports_device(
           *a_lst = arr[6], *a_henc = arr[7], *a_hct = arr[8], *a_hst = arr[10], *a_sst = arr[11];
   uint32_t *a_lcl = (uint32_t*)arr[5], *a_hcl = (uint32_t*)arr[9];
   uint64_t* a_t = (uint64_t*)arr[12];
-  const uint32_t mstride = p.kind == PRIO3_SUMVEC ? p.length : 1;
-  const uint32_t rl = p.jr_len ? 80 : 48;
+  const uint32_t mstride = client_meas_stride(p), rl = client_rand_stride(p);
   for (uint64_t off = 0; off < n && rc == PRIO3_OK; off += chunk) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
     const uint8_t* ids = d_report_ids + 16 * off;
     k_client_round_times<<<(m + 255) / 256, 256, 0, st>>>(d_times + off, time_precision, a_t, m);
     ShardIn in{d_measurements + (size_t)mstride * off, ids, d_rand + (size_t)rl * off};
     ShardOut out{a_pub, a_lin, a_hsh, a_sst};
-    rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, false, st);
-    if (rc == PRIO3_OK) rc = shard_launch(p, m, (uint32_t)chunk, slab->base, in, out, true, st);
+    rc = shard_launch(p, e->mp, m, (uint32_t)chunk, slab->base, in, out, false, st);
+    if (rc == PRIO3_OK) rc = shard_launch(p, e->mp, m, (uint32_t)chunk, slab->base, in, out, true, st);
     if (rc != PRIO3_OK) break;
     int hrc = janus_hpke_seal_input_shares_device(lsl, m, task_id, d_sk_e_leader + 32 * off, ids,
                                                   a_t, psl ? a_pub : nullptr, psl, a_lin, L,

@@ -899,9 +899,12 @@ class HelperEngine:
         return load_library().prio3_client_rand_len(C.byref(self.vdaf.params()))
 
     def _client_shapes(self, n, measurements, nonces, rand):
-        if self.vdaf.kind not in (PRIO3_COUNT, PRIO3_SUM, PRIO3_SUMVEC, PRIO3_HISTOGRAM):
-            raise NotImplementedError("the client role takes Count, Sum, SumVec and Histogram")
-        mstride = self.vdaf.length if self.vdaf.kind == PRIO3_SUMVEC else 1
+        if self.vdaf.kind not in (PRIO3_COUNT, PRIO3_SUM, PRIO3_SUMVEC, PRIO3_HISTOGRAM,
+                                  PRIO3_SUMVEC_F64_MP):
+            raise NotImplementedError(
+                "the client role does not take FixedPointBoundedL2VecSum (it takes Count, Sum, "
+                "SumVec, Histogram and SumVecField64MultiproofHmacSha256Aes128)")
+        mstride = self.vdaf.length if self.vdaf.kind in (PRIO3_SUMVEC, PRIO3_SUMVEC_F64_MP) else 1
         if tuple(measurements.shape) not in ((n, mstride),) + (((n,),) if mstride == 1 else ()):
             raise ValueError(f"measurements must be [{n}, {mstride}]")
         if tuple(nonces.shape) != (n, 16):
