@@ -258,6 +258,79 @@ int prio3_helper_aggregate_init_batch_ex(
     const uint32_t* segment_ids, const uint8_t* accept_mask, uint32_t n_segments,
     uint8_t* prep_msgs_out, uint8_t* status_out, uint8_t* agg_shares_out, uint64_t* counts_out);
 
+/* ---- One-call helper job ---- */
+/* A whole helper aggregation job as AggregationJobWriter needs it (aggregation_job_writer.rs:
+ * 540-695, aggregator.rs:1765-1773), in ONE trip through the executor: the job index
+ * (prio3_job_index below: batch-identifier index, BatchCollected rejections, duplicate-ID verdict),
+ * the loop body of prio3_helper_aggregate_init_batch_ex, and the per-batch ReportIdChecksum and
+ * client-timestamp interval of prio3_batch_metadata.  The result is byte for byte what this
+ * composition of the three calls gives, and every rule of their sections holds unchanged:
+ *   prio3_job_index(report_ids, times, time_precision, closed_intervals, k, max_segments, ...);
+ *   accept[i] = the job index's accept byte AND accept_mask[i] != 0 (NULL mask: all ones);
+ *   prio3_helper_aggregate_init_batch_ex(..., segment_ids, accept, n_segments = max_segments, ...);
+ *   prio3_batch_metadata(report_ids, times, status, accept, segment_ids, max_segments, ...).
+ * So the aggregate, count, checksum and interval rows are sized for max_segments segments (rows
+ * >= info->n_segments: zero, count 0, Interval::EMPTY); at overflow every segment id is 0xFFFFFFFF
+ * and nothing is counted while statuses and prepare messages stay valid; a duplicate ID marks a
+ * report and rejects nothing; a report the host mask, a closed batch or its status excludes is in
+ * no aggregate, count or checksum but still widens its batch's interval.  accept_mask (nullable)
+ * carries the datastore's replay survivors, which stay the host's.
+ * A job of at most PRIO3_JOB_GROUP_MAX_REPORTS reports and PRIO3_JOB_GROUP_MAX_SEGMENTS segments
+ * (and max_segments aggregate shares within one group's staging) is indexed by one workgroup in
+ * front of the coalesced group launch that opens, prepares and accumulates it, and its metadata
+ * rows are made behind that accumulate; jobs that carry an index request share launches with each
+ * other.  A larger job runs the three calls from inside this one -- no size is refused.
+ * out->segment_starts, reject, duplicate, checksums and intervals may each be NULL (prep_msgs too
+ * for an instance without joint randomness); closed_intervals is read before the call returns.
+ * Errors: those of the three calls (PRIO3_EINVAL for max_segments 0 or above 4096, k > 1024,
+ * n > 2^30, a missing buffer). */
+enum { PRIO3_JOB_GROUP_MAX_REPORTS = 4096, PRIO3_JOB_GROUP_MAX_SEGMENTS = 64 };
+typedef struct {            /* what the job index found (section "Job index" below) */
+  uint32_t n_segments;      /* distinct batch identifiers found, if <= max_segments */
+  uint32_t overflow;        /* 1: more than max_segments distinct identifiers */
+  uint32_t n_duplicates;    /* reports whose ID also occurs at a lower index */
+  uint32_t first_duplicate; /* lowest such index; 0xFFFFFFFF if none */
+  uint32_t n_closed;        /* reports in a closed batch */
+  uint32_t n_time_errors;   /* reports whose batch interval overflows u64 */
+} prio3_job_index_info;
+typedef struct {
+  struct janus_hpke_opener* opener;          /* as prio3_helper_aggregate_init_batch_ex */
+  struct janus_hpke_opener* fallback_opener; /* nullable */
+  uint64_t report_deadline;                  /* UINT64_MAX: no check */
+  uint32_t n;
+  int32_t require_taskprov;
+  const uint8_t* task_id;                    /* [32] */
+  const uint8_t* report_ids;                 /* [n][16] */
+  const uint64_t* times;                     /* [n] */
+  const uint8_t* public_shares;              /* [n][public_share_len] */
+  const uint8_t* enc;                        /* [n][Nenc] */
+  const uint8_t* ct;                         /* [n][ct_stride] */
+  const uint32_t* ct_len;                    /* [n] */
+  const uint8_t* leader_prep_shares;         /* [n][prep_share_len] */
+  uint32_t ct_stride;
+  uint32_t k;                                /* closed intervals */
+  uint64_t time_precision;                   /* 0: a fixed-size task */
+  const uint64_t* closed_intervals;          /* host [k][2] (start, duration); NULL when k = 0 */
+  const uint8_t* accept_mask;                /* host [n], nullable */
+  uint32_t max_segments;
+  uint32_t reserved;                         /* 0 */
+} prio3_helper_job_in;
+typedef struct {
+  uint32_t* segment_ids;                     /* [n] */
+  uint64_t* segment_starts;                  /* [max_segments], nullable */
+  uint8_t* reject;                           /* [n], nullable */
+  uint8_t* duplicate;                        /* [n], nullable */
+  prio3_job_index_info* info;
+  uint8_t* prep_msgs;                        /* [n][prep_msg_len] */
+  uint8_t* status;                           /* [n] */
+  uint8_t* agg_shares;                       /* [max_segments][agg_share_len] */
+  uint64_t* counts;                          /* [max_segments] */
+  uint8_t* checksums;                        /* [max_segments][32], nullable */
+  uint64_t* intervals;                       /* [max_segments][2], nullable */
+} prio3_helper_job_out;
+int prio3_helper_aggregate_job(prio3_engine* engine, const prio3_helper_job_in* job,
+                               const prio3_helper_job_out* out);
+
 /* Parity-only: copies the n output shares (n x agg_share_len). */
 int prio3_debug_output_shares(prio3_batch* batch, uint8_t* out);
 void prio3_batch_free(prio3_batch* batch);
@@ -360,14 +433,7 @@ int prio3_batch_metadata(prio3_engine* engine, uint32_t n, const uint8_t* report
  * Device form: stream-ordered, no host synchronisation, scratch from the GPU's pool (8 n to 16 n
  * bytes for the ID table); d_report_ids 16-byte aligned.  Host form: a plain blocking call. */
 enum { PRIO3_REJECT_BATCH_COLLECTED = 0x80 };
-typedef struct {
-  uint32_t n_segments;      /* distinct batch identifiers found, if <= max_segments */
-  uint32_t overflow;        /* 1: more than max_segments distinct identifiers */
-  uint32_t n_duplicates;    /* reports whose ID also occurs at a lower index */
-  uint32_t first_duplicate; /* lowest such index; 0xFFFFFFFF if none */
-  uint32_t n_closed;        /* reports in a closed batch */
-  uint32_t n_time_errors;   /* reports whose batch interval overflows u64 */
-} prio3_job_index_info;
+/* prio3_job_index_info: declared above, ahead of prio3_helper_aggregate_job */
 int prio3_device_job_index(prio3_engine* engine, uint32_t n, const uint8_t* d_report_ids,
                            const uint64_t* d_times, uint64_t time_precision,
                            const uint64_t* closed_intervals, uint32_t k, uint32_t max_segments,

@@ -43,6 +43,10 @@ Pool& pool() {
 template <class F>
 double run_pool(int threads, int jobs, F job) {
   Pool& P = pool();
+  // one caller at a time: the pool has one work slot, and a second caller arriving inside a run
+  // would replace the work its threads are still picking up
+  static std::mutex call_mu;
+  std::lock_guard<std::mutex> call(call_mu);
   std::atomic<int> next{0}, failed{0};
   std::unique_lock<std::mutex> lk(P.mu);
   while (P.threads < threads) {
@@ -240,6 +244,111 @@ double janus_jobs_run_init(prio3_engine** engines, int n_engines, const prio3_si
     }
     counts_out[j] = cnt;
     return rc == 0;
+  });
+}
+
+// A whole helper job as AggregationJobWriter needs it, per job of the same report windows as
+// janus_jobs_run_init: batch-identifier index (time_precision, closed[k][2], max_segments), the
+// loop body, and the per-batch checksums and intervals.  form 0: the three calls a host-buffer
+// caller makes today -- prio3_job_index, prio3_helper_aggregate_init_batch_ex with the index's
+// segment ids and accept bytes, prio3_batch_metadata; 1: prio3_helper_aggregate_job; 2: the _ex
+// call alone with one segment and no index or metadata (what janus_jobs_run_init times); 3: the
+// _ex call alone over the segment ids and reject bytes an earlier index of the same jobs left in
+// seg_out / reject_out (inputs in this form), with max_segments rows: form 0 without its two
+// blocking calls, which separates what the job's segments cost the accumulate from what the index
+// and the metadata cost.
+// Per job j: seg_out / status_out / reject_out / dup_out [jobs * job_size], counts_out
+// [jobs][max_segments], agg_out [jobs][max_segments][agg_len], ck_out [jobs][max_segments][32],
+// iv_out [jobs][max_segments][2], starts_out [jobs][max_segments], info_out [jobs] (form 2 fills
+// status, and row 0 of counts and agg).
+double janus_jobs_run_job(prio3_engine** engines, int n_engines, const prio3_sizes_t* szp,
+                          janus_hpke_opener* opener, const uint8_t* task_ids, int threads,
+                          int jobs, int job_size, uint32_t pool, const uint8_t* nonces,
+                          const uint8_t* pub, const uint64_t* times, const uint8_t* enc,
+                          uint32_t nenc, const uint8_t* ct, const uint32_t* ct_len,
+                          uint32_t ct_stride, const uint8_t* lps, uint64_t time_precision,
+                          const uint64_t* closed, uint32_t k, uint32_t max_segments,
+                          uint32_t* seg_out, uint64_t* starts_out, uint8_t* reject_out,
+                          uint8_t* dup_out, prio3_job_index_info* info_out, uint8_t* status_out,
+                          uint64_t* counts_out, uint8_t* agg_out, uint8_t* ck_out,
+                          uint64_t* iv_out, int form) {
+  const prio3_sizes_t sz = *szp;
+  const uint32_t span = pool - (uint32_t)job_size + 1;
+  const size_t S = max_segments;
+  return run_pool(threads, jobs, [&](int j) {
+    thread_local std::vector<uint8_t> msgs, acc;
+    msgs.resize((size_t)job_size * (sz.prep_msg_len ? sz.prep_msg_len : 1));
+    const uint32_t t = (uint32_t)(j % n_engines);
+    const size_t r0 = t * (size_t)pool + (((uint64_t)(j / n_engines) * job_size) % span);
+    const size_t o = (size_t)j * job_size;
+    const uint32_t n = (uint32_t)job_size;
+    const uint8_t* jp = sz.public_share_len ? pub + (size_t)sz.public_share_len * r0 : nullptr;
+    const uint8_t* tid = task_ids + 32 * (size_t)t;
+    uint8_t* agg = agg_out + (size_t)sz.agg_share_len * S * j;
+    uint64_t* cnt = counts_out + S * j;
+    if (form == 3) {  // seg_out / reject_out are inputs here: a finished index of the same job
+      acc.resize(n);
+      for (uint32_t i = 0; i < n; i++)
+        acc[i] = seg_out[o + i] != 0xFFFFFFFFu && reject_out[o + i] == 0;
+      return prio3_helper_aggregate_init_batch_ex(
+                 engines[t], opener, nullptr, UINT64_MAX, n, tid, 0, nonces + 16 * r0, times + r0,
+                 jp, enc + (size_t)nenc * r0, ct + (size_t)ct_stride * r0, ct_len + r0, ct_stride,
+                 lps + (size_t)sz.prep_share_len * r0, seg_out + o, acc.data(), max_segments,
+                 msgs.data(), status_out + o, agg, cnt) == PRIO3_OK;
+    }
+    if (form == 2)
+      return prio3_helper_aggregate_init_batch_ex(
+                 engines[t], opener, nullptr, UINT64_MAX, n, tid, 0, nonces + 16 * r0, times + r0,
+                 jp, enc + (size_t)nenc * r0, ct + (size_t)ct_stride * r0, ct_len + r0, ct_stride,
+                 lps + (size_t)sz.prep_share_len * r0, nullptr, nullptr, 1, msgs.data(),
+                 status_out + o, agg, cnt) == PRIO3_OK;
+    if (form == 1) {
+      prio3_helper_job_in in{};
+      in.opener = opener;
+      in.report_deadline = UINT64_MAX;
+      in.n = n;
+      in.task_id = tid;
+      in.report_ids = nonces + 16 * r0;
+      in.times = times + r0;
+      in.public_shares = jp;
+      in.enc = enc + (size_t)nenc * r0;
+      in.ct = ct + (size_t)ct_stride * r0;
+      in.ct_len = ct_len + r0;
+      in.leader_prep_shares = lps + (size_t)sz.prep_share_len * r0;
+      in.ct_stride = ct_stride;
+      in.k = k;
+      in.time_precision = time_precision;
+      in.closed_intervals = closed;
+      in.max_segments = max_segments;
+      prio3_helper_job_out out{};
+      out.segment_ids = seg_out + o;
+      out.segment_starts = starts_out + S * j;
+      out.reject = reject_out + o;
+      out.duplicate = dup_out + o;
+      out.info = info_out + j;
+      out.prep_msgs = msgs.data();
+      out.status = status_out + o;
+      out.agg_shares = agg;
+      out.counts = cnt;
+      out.checksums = ck_out + 32 * S * j;
+      out.intervals = iv_out + 2 * S * j;
+      return prio3_helper_aggregate_job(engines[t], &in, &out) == PRIO3_OK;
+    }
+    acc.resize(n);
+    int rc = prio3_job_index(engines[t], n, nonces + 16 * r0, times + r0, time_precision, closed,
+                             k, max_segments, seg_out + o, starts_out + S * j, acc.data(),
+                             reject_out + o, dup_out + o, info_out + j);
+    if (rc == PRIO3_OK)
+      rc = prio3_helper_aggregate_init_batch_ex(
+          engines[t], opener, nullptr, UINT64_MAX, n, tid, 0, nonces + 16 * r0, times + r0, jp,
+          enc + (size_t)nenc * r0, ct + (size_t)ct_stride * r0, ct_len + r0, ct_stride,
+          lps + (size_t)sz.prep_share_len * r0, seg_out + o, acc.data(), max_segments,
+          msgs.data(), status_out + o, agg, cnt);
+    if (rc == PRIO3_OK)
+      rc = prio3_batch_metadata(engines[t], n, nonces + 16 * r0, times + r0, status_out + o,
+                                acc.data(), seg_out + o, max_segments, ck_out + 32 * S * j,
+                                iv_out + 2 * S * j);
+    return rc == PRIO3_OK;
   });
 }
 

@@ -645,6 +645,10 @@ struct Run {
   // the retry pass of a group with a fallback keypair: [0] the count, [1 .. n] the reports to open
   // again (k_hpke_retry_list)
   uint32_t* hretry = nullptr;
+  // groups whose launch makes the job index and the batch metadata (RUN_JIX): per-segment
+  // checksums [nseg][8] and intervals [nseg][2]
+  uint32_t* gck = nullptr;
+  unsigned long long* giv = nullptr;
 };
 
 struct prio3_engine {

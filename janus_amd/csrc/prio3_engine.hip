@@ -456,6 +456,11 @@ static size_t run_carve(Run* R, unsigned flags, uint8_t* base) {
     take(&R->hpt, (size_t)R->hpke_stride * n);
     take(&R->hretry, 4 * (n + 1));
   }
+  if (flags & RUN_JIX) {
+    const size_t S = R->nseg ? R->nseg : 1;
+    take(&R->gck, 32 * S);
+    take(&R->giv, 16 * S);
+  }
   if (flags & RUN_FUSED) {
     // sized for 32-report waves (k_prep_hp); the one-lane kernels use the first half
     const size_t waves = (n + 31) / 32, M = d.meas_len, chunks = (waves + WCH - 1) / WCH;
@@ -601,6 +606,10 @@ uint64_t exec_job_key(const ExecJob* j) {
       h = fnv(h, f, sizeof f);
     }
   }
+  if (j->jix) {  // jobs whose index the launch makes share no group with jobs that bring theirs
+    const uint64_t u = 0x4A4F42494E444558ull;
+    h = fnv(h, &u, sizeof u);
+  }
   return h;
 }
 
@@ -659,6 +668,30 @@ void engine_io_layout(const prio3_engine* e, uint32_t cap, IoLayout* L, const Ex
     off += 32 * (size_t)HPKE_MAX_TASKS;
     L->dtab_off = off;
     off += 8 * (size_t)HPKE_MAX_TASKS;
+  }
+  L->jix = job && job->jix;
+  if (L->jix) {  // prio3_helper_aggregate_job: descriptors, closed intervals, index + metadata rows
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t S = L->max_seg;
+    off = up(off);
+    L->jdesc_off = off;
+    off += up(sizeof(JixJobDesc) * S);
+    L->jclosed_off = off;
+    off += 16 * (size_t)JIX_GROUP_CLOSED;
+    L->jseg_off = off;
+    off += up(4 * (size_t)cap);
+    L->jrej_off = off;
+    off += up(cap);
+    L->jdup_off = off;
+    off += up(cap);
+    L->jstart_off = off;
+    off += 8 * S;
+    L->jinfo_off = off;
+    off += up(sizeof(prio3_job_index_info) * S);
+    L->ck_off = off;
+    off += 32 * S;
+    L->iv_off = off;
+    off += 16 * S;
   }
   L->bytes = off;
 }
@@ -768,9 +801,13 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
   else
     engine_io_layout(lead, g.cap, &L);
   const bool sealed = L.ct_stride > 0 && g.opener;
+  // prio3_helper_aggregate_job groups: the launch makes the jobs' index and metadata itself
+  const bool jix = g.njix > 0 && agg && sealed && L.jix;
+  if (g.njix && !jix) return PRIO3_EINVAL;
   int rc = group_begin(lead, dg_, g.jobs, own_queue, g.n,
                        RUN_SCRATCH | RUN_IO | (agg ? (unsigned)RUN_AGG_IO : 0u) |
-                           (fuse ? (unsigned)RUN_FUSED : 0u) | (sealed ? (unsigned)RUN_HPKE : 0u),
+                           (fuse ? (unsigned)RUN_FUSED : 0u) | (sealed ? (unsigned)RUN_HPKE : 0u) |
+                           (jix ? (unsigned)RUN_JIX : 0u),
                        agg ? g.nseg : 0, sealed ? L.ct_stride : 0, gr);
   if (rc) return rc;
   Run* R = gr->R;
@@ -778,6 +815,28 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
   auto fail = [&](int code) { return group_fail(gr, code); };
   const uint8_t* hd = g.stg_dev;
   InPtrs in{hd + L.off[0], L.len[1] ? hd + L.off[1] : nullptr, hd + L.off[2], R->leader};
+  if (jix) {
+    // first on the stream: each job's workgroup turns its staged IDs, times, closed intervals and
+    // host accept bytes into the group segment ids and accept bytes in the run (every column, the
+    // pad columns included), where the prepare, the accumulate and the metadata below read them,
+    // and into the job's index outputs in the staging
+    uint8_t* sd = g.stg_dev;
+    JixGroupArgs a{};
+    a.desc = (const JixJobDesc*)(hd + L.jdesc_off);
+    a.closed = (const unsigned long long*)(hd + L.jclosed_off);
+    a.ids = hd + L.off[0];
+    a.times = (const unsigned long long*)(hd + L.time_off);
+    a.accept = hd + L.accept_off;
+    a.ids_dev = R->nonces;
+    a.gseg = R->gseg;
+    a.gaccept = R->gaccept;
+    a.seg_out = (uint32_t*)(sd + L.jseg_off);
+    a.rej_out = sd + L.jrej_off;
+    a.dup_out = sd + L.jdup_off;
+    a.starts_out = (unsigned long long*)(sd + L.jstart_off);
+    a.info_out = (prio3_job_index_info*)(sd + L.jinfo_off);
+    if (launch_jix_group(lead, g.njix, a, st) != PRIO3_OK) return fail(PRIO3_EDEVICE);
+  }
   if (sealed) {
     // the helper's loop body from its first line (aggregator.rs:1847-1990): each report's input
     // share opened, decoded and checked into the run's helper-share buffer, which the prepare
@@ -824,13 +883,14 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
     in.vk_slot = (const uint16_t*)(hd + L.slot_off);
     in.vk_tab = (const uint4*)(hd + L.tab_off);
   }
-  if (agg) R->seg = (const uint32_t*)(hd + L.seg_off);  // the fused XOF's segment check
+  // the fused XOF's segment check (an indexed group's ids are made on the device, in the run)
+  if (agg) R->seg = jix ? R->gseg : (const uint32_t*)(hd + L.seg_off);
   // the leader prep shares (and the segment ids / accept bytes of the fix-up pass)
   PullRanges pr{};
   pr.src[0] = hd + L.off[3];
   pr.dst[0] = R->leader;
   pr.bytes[0] = L.len[3] * g.n;
-  if (agg) {
+  if (agg && !jix) {  // (k_jix_group wrote an indexed group's straight into the run)
     pr.src[1] = hd + L.seg_off;
     pr.dst[1] = (uint8_t*)R->gseg;
     pr.bytes[1] = 4 * (size_t)g.n;
@@ -856,6 +916,21 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
               : run_accumulate(lead, R, 0, g.n, R->status, R->gseg, R->gaccept, g.nseg, R->gagg,
                                (uint64_t*)R->gcnt, st);
     if (rc) return fail(rc);
+  }
+  if (jix) {
+    // the rest of the BatchAggregation update over the group's columns and segments, from the
+    // merged statuses; the rows go back by a copy launch of their own
+    rc = launch_batch_metadata(lead, g.n, R->nonces, (const uint64_t*)(hd + L.time_off), R->status,
+                               R->gaccept, R->gseg, g.nseg, R->gck, R->giv, st);
+    if (rc) return fail(rc);
+    PullRanges m{};
+    m.src[0] = (const uint8_t*)R->gck;
+    m.dst[0] = g.stg_dev + L.ck_off;
+    m.bytes[0] = 32 * (size_t)g.nseg;
+    m.src[1] = (const uint8_t*)R->giv;
+    m.dst[1] = g.stg_dev + L.iv_off;
+    m.bytes[1] = 16 * (size_t)g.nseg;
+    if (!pull_outputs(m, st)) return fail(PRIO3_EDEVICE);
   }
   {  // the outputs go back by one copy launch writing the mapped staging
     uint8_t* sd = g.stg_dev;
@@ -1871,6 +1946,83 @@ int prio3_helper_aggregate_init_batch_ex(
                                require_taskprov, report_ids, times, public_shares, enc, ct,
                                ct_len, ct_stride, leader_prep_shares, segment_ids, accept_mask,
                                n_segments, prep_msgs_out, status_out, agg_shares_out, counts_out);
+}
+
+// The three calls prio3_helper_aggregate_job stands for, as a caller would make them: what a job
+// outside the in-group limits (and an empty one) runs, and what every other job's result equals.
+static int helper_job_three_calls(prio3_engine* e, const prio3_helper_job_in& in,
+                                  const prio3_helper_job_out& out) {
+  const uint32_t n = in.n, S = in.max_segments;
+  std::vector<uint8_t> acc(n ? n : 1);
+  int rc = prio3_job_index(e, n, in.report_ids, in.times, in.time_precision, in.closed_intervals,
+                           in.k, S, out.segment_ids, out.segment_starts, acc.data(), out.reject,
+                           out.duplicate, out.info);
+  if (rc) return rc;
+  if (in.accept_mask)
+    for (uint32_t i = 0; i < n; i++) acc[i] = acc[i] && in.accept_mask[i];
+  rc = prio3_helper_aggregate_init_batch_ex(
+      e, in.opener, in.fallback_opener, in.report_deadline, n, in.task_id, in.require_taskprov,
+      in.report_ids, in.times, in.public_shares, in.enc, in.ct, in.ct_len, in.ct_stride,
+      in.leader_prep_shares, out.segment_ids, acc.data(), S, out.prep_msgs, out.status,
+      out.agg_shares, out.counts);
+  if (rc) return rc;
+  if (!out.checksums && !out.intervals) return PRIO3_OK;
+  return prio3_batch_metadata(e, n, in.report_ids, in.times, out.status, acc.data(),
+                              out.segment_ids, S, out.checksums, out.intervals);
+}
+
+int prio3_helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
+                               const prio3_helper_job_out* out) {
+  TraceSpan span_("handle_aggregate_init_generic threadpool task");
+  if (!e || !in || !out || !out->info) return PRIO3_EINVAL;
+  const uint32_t n = in->n, S = in->max_segments;
+  // the argument rules of the three calls, checked before any of them runs
+  if (n > (1u << 30) || S == 0 || S > 4096 || in->k > 1024 || (in->k && !in->closed_intervals) ||
+      !in->opener || !in->task_id || !out->agg_shares || !out->counts || in->ct_stride == 0 ||
+      in->ct_stride % 16 != 0 ||
+      (n && (!in->report_ids || !in->times || !in->enc || !in->ct || !in->ct_len ||
+             !in->leader_prep_shares || !out->status || !out->segment_ids)))
+    return PRIO3_EINVAL;
+  if (in->fallback_opener && hpke_opener_kem(in->fallback_opener) != hpke_opener_kem(in->opener))
+    return PRIO3_EINVAL;
+  if (fpvec_refused(e)) return PRIO3_EUNSUPPORTED;
+  const DevParams& d = e->dp;
+  if (d.public_share_len != 0 && d.public_share_len != 32 && d.public_share_len != 64)
+    return PRIO3_EUNSUPPORTED;
+  if (n && d.jr_len && (!in->public_shares || !out->prep_msgs)) return PRIO3_EINVAL;
+  IoLayout L1;
+  engine_io_layout(e, 1, &L1);
+  if (n == 0 || n > JIX_GROUP_MAX_N || S > JIX_GROUP_MAX_SEG || S > L1.max_seg)
+    return helper_job_three_calls(e, *in, *out);
+  e = place(e, n);
+  ExecJob job = helper_job(e, n, in->report_ids, in->public_shares, nullptr,
+                           in->leader_prep_shares, out->prep_msgs, out->status, nullptr,
+                           in->accept_mask, S, out->agg_shares, out->counts);
+  job.opener = in->opener;
+  job.task_id = in->task_id;
+  job.times = in->times;
+  job.enc = in->enc;
+  job.ct = in->ct;
+  job.ct_len = in->ct_len;
+  job.ct_stride = in->ct_stride;
+  job.require_taskprov = in->require_taskprov ? 1 : 0;
+  job.fallback = in->fallback_opener;
+  job.deadline = in->report_deadline;
+  job.jix = true;
+  job.precision = in->time_precision;
+  job.closed = in->closed_intervals;
+  job.nclosed = in->k;
+  job.jseg_out = out->segment_ids;
+  job.jstarts_out = out->segment_starts;
+  job.jrej_out = out->reject;
+  job.jdup_out = out->duplicate;
+  job.jinfo_out = out->info;
+  job.ck_out = out->checksums;
+  job.iv_out = out->intervals;
+  const int rc = exec_submit(&job);
+  if (rc) return rc;
+  run_release(job.run, nullptr, false);
+  return PRIO3_OK;
 }
 
 int prio3_accumulate(prio3_batch* b, const uint32_t* segment_ids, const uint8_t* accept_mask,

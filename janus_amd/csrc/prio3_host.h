@@ -63,6 +63,7 @@ enum : unsigned {
   RUN_FUSED = 16,   // fused-accumulate partials (prio3_device_prepare_aggregate, Histogram)
   RUN_AGG_IO = 32,  // group segment ids, accept bytes, aggregate shares + counts (executor)
   RUN_HPKE = 64,    // open statuses + plaintext scratch of a sealed-input group (executor)
+  RUN_JIX = 128,    // checksum + interval rows of a group of prio3_helper_aggregate_job jobs
 };
 
 static inline bool own_out(const DevParams& d) {  // the output share is not the measurement share
@@ -138,6 +139,28 @@ int launch_batch_metadata(prio3_engine* e, uint32_t n, const uint8_t* d_report_i
 int launch_combine_metadata(prio3_engine* e, uint32_t k, uint32_t n_segments,
                             const uint32_t* ck_in, const unsigned long long* iv_in,
                             uint32_t* ck_out, unsigned long long* iv_out, hipStream_t st);
+
+// ---- prio3_jobindex.hip ----
+// k_jix_group over the n_jobs descriptors of a group of prio3_helper_aggregate_job jobs, one
+// workgroup per job: desc / closed / ids / times / accept are the staged inputs (mapped), ids_dev
+// a device copy of the IDs it leaves for its own probes and the metadata launch, gseg / gaccept
+// the run's group segment ids and accept bytes (every column of the group is written), and
+// seg_out .. info_out the index outputs in the staging.
+struct JixGroupArgs {
+  const JixJobDesc* desc;
+  const unsigned long long* closed;
+  const uint8_t* ids;
+  const unsigned long long* times;
+  const uint8_t* accept;
+  uint8_t* ids_dev;
+  uint32_t* gseg;
+  uint8_t* gaccept;
+  uint32_t* seg_out;
+  uint8_t *rej_out, *dup_out;
+  unsigned long long* starts_out;
+  prio3_job_index_info* info_out;
+};
+int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st);
 
 // ---- prio3_client.hip: the generic leader kernels ----
 extern "C" int launch_leader_init(const DevParams& dp, const uint8_t* d_nonces,

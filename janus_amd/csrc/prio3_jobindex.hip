@@ -347,6 +347,208 @@ __global__ __launch_bounds__(256) void k_jix_assign(uint32_t n, const uint8_t* i
   }
 }
 
+// ---- the job index of a group of host-buffer jobs (prio3_helper_aggregate_job) ----
+// One workgroup per job, everything in LDS, first on the group's stream: only the launch order
+// orders it against the open, the prepare and the accumulate that read what it writes.  The same
+// steps as the four kernels above at job size (n <= JIX_GROUP_MAX_N reports, max_segments <=
+// JIX_GROUP_MAX_SEG):
+//   IDs      the job's staged IDs are copied into the run (ids_dev) and every report inserts its
+//            index into s_slot, 2 next_pow2(n) slots keyed by the 16 ID bytes, atomicMin keeping
+//            the lowest index of an ID -- so duplicate[i] is "some j < i has these bytes";
+//   starts   every report inserts its start into s_tab (a compare-and-swap on 64-bit keys, 4 x
+//            JIX_GROUP_MAX_SEG slots: at most half full below the overflow limit), the distinct
+//            ones are gathered into s_key, sorted (bitonic) and the closed flag of each is decided
+//            once against the job's k intervals;
+//   reports  the rank of each report's start by binary search: R->gseg = seg0 + rank (or
+//            0xFFFFFFFF), R->gaccept = index accept & staged host accept, and into the staging the
+//            job-local segment ids, reject, duplicate, segment starts and the info struct.
+// Every probe loop is bounded by its table; the outputs do not depend on the order of arrival.
+constexpr uint32_t JIXG_T = 256;
+constexpr uint32_t JIXG_SLOTS = 2 * JIX_GROUP_MAX_N;   // 32 KiB of report indices
+constexpr uint32_t JIXG_TAB = 4 * JIX_GROUP_MAX_SEG;   // start table (2 KiB)
+constexpr uint32_t JIXG_KEYS = 2 * JIX_GROUP_MAX_SEG;  // sorted starts, padded to a power of two
+
+__global__ __launch_bounds__(JIXG_T) void k_jix_group(JixGroupArgs A) {
+  __shared__ uint32_t s_slot[JIXG_SLOTS];
+  __shared__ unsigned long long s_tab[JIXG_TAB];
+  __shared__ unsigned long long s_key[JIXG_KEYS];
+  __shared__ uint8_t s_closed[JIX_GROUP_MAX_SEG];
+  __shared__ uint32_t s_found, s_count, s_dup, s_first, s_nclosed, s_err;
+  const JixJobDesc D = A.desc[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  // the host checked the limits; a descriptor outside them writes its columns as excluded
+  const bool sane = D.n <= JIX_GROUP_MAX_N && D.max_segments >= 1 &&
+                    D.max_segments <= JIX_GROUP_MAX_SEG && D.k <= JIX_MAX_CLOSED;
+  const uint32_t n = sane ? D.n : 0u, S = sane ? D.max_segments : 0u;
+  const unsigned long long precision = D.precision;
+  const uint8_t* ids = A.ids_dev + 16 * (size_t)D.c0;  // the job's IDs once they are copied
+  const unsigned long long* times = A.times + D.c0;
+  uint32_t icap = 4;
+  while (icap < 2 * n) icap <<= 1;  // <= JIXG_SLOTS
+  const uint32_t imask = icap - 1, tmask = JIXG_TAB - 1;
+  // pad columns before and after the job's reports (and all of an insane job's): excluded
+  for (uint32_t c = D.pad0 + tid; c < D.end; c += JIXG_T)
+    if (c < D.c0 || c >= D.c0 + n) {
+      A.gseg[c] = 0xffffffffu;
+      A.gaccept[c] = 0;
+    }
+  for (uint32_t h = tid; h < icap; h += JIXG_T) s_slot[h] = JIX_NO_INDEX;
+  for (uint32_t h = tid; h < JIXG_TAB; h += JIXG_T) s_tab[h] = JIX_NO_KEY;
+  if (tid == 0) {
+    s_found = 0;
+    s_count = 0;
+    s_dup = 0;
+    s_first = 0xffffffffu;
+    s_nclosed = 0;
+    s_err = 0;
+  }
+  for (uint32_t i = tid; i < n; i += JIXG_T)
+    *(uint4*)(A.ids_dev + 16 * (size_t)(D.c0 + i)) =
+        *(const uint4*)(A.ids + 16 * (size_t)(D.c0 + i));
+  __threadfence_block();
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += JIXG_T) {
+    unsigned long long start;
+    if (precision && jix_start(times[i], precision, &start)) {
+      uint32_t h = jix_hash_start(start) & tmask;
+      for (uint32_t p = 0; p <= tmask; p++) {
+        if (__hip_atomic_load(&s_found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > S)
+          break;  // more than max_segments starts are known: the job ends in overflow
+        unsigned long long cur = atomicCAS(s_tab + h, JIX_NO_KEY, start);
+        if (cur == JIX_NO_KEY) {
+          atomicAdd(&s_found, 1u);
+          break;
+        }
+        if (cur == start) break;
+        h = (h + 1) & tmask;
+      }
+    }
+    const uint4 id = jix_id(ids, i);
+    uint32_t h = jix_hash_id(id) & imask;
+    for (uint32_t p = 0; p <= imask; p++) {
+      const uint32_t j = atomicCAS(s_slot + h, JIX_NO_INDEX, i);
+      if (j == JIX_NO_INDEX) break;
+      if (jix_same(jix_id(ids, j < n ? j : i), id)) {  // j < n: a slot only holds report indices
+        if (i < j) atomicMin(s_slot + h, i);
+        break;
+      }
+      h = (h + 1) & imask;
+    }
+  }
+  __syncthreads();
+  const uint32_t found = precision ? s_found : (n ? 1u : 0u);
+  const bool overflow = found > S;  // block-uniform
+  if (precision && !overflow) {
+    // found <= max_segments keys are in the table: gathered, padded to a power of two, sorted
+    for (uint32_t h = tid; h < JIXG_TAB; h += JIXG_T) {
+      const unsigned long long key = s_tab[h];
+      if (key != JIX_NO_KEY) {
+        const uint32_t at = atomicAdd(&s_count, 1u);
+        if (at < JIXG_KEYS) s_key[at] = key;
+      }
+    }
+    uint32_t P = 1;
+    while (P < found) P <<= 1;  // <= JIX_GROUP_MAX_SEG
+    for (uint32_t s = found + tid; s < P; s += JIXG_T) s_key[s] = JIX_NO_KEY;
+    __syncthreads();
+    for (uint32_t size = 2; size <= P; size <<= 1) {
+      for (uint32_t step = size >> 1; step > 0; step >>= 1) {
+        for (uint32_t t = tid; t < P / 2; t += JIXG_T) {
+          const uint32_t lo = 2 * t - (t & (step - 1)), hi = lo + step;  // lo has bit `step` clear
+          const bool up = (lo & size) == 0;
+          const unsigned long long a = s_key[lo], b = s_key[hi];
+          if ((a > b) == up) {
+            s_key[lo] = b;
+            s_key[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (uint32_t s = tid; s < S; s += JIXG_T) {
+      bool closed = false;
+      if (s < found) {
+        const unsigned long long start = s_key[s];
+        for (uint32_t j = 0; j < D.k; j++) {
+          const unsigned long long a = A.closed[2 * (size_t)(D.closed0 + j)],
+                                   d = A.closed[2 * (size_t)(D.closed0 + j) + 1];
+          closed |= start >= a && start - a < d;  // [a, a + d), no wrap-around
+        }
+      }
+      s_closed[s] = closed;
+      A.starts_out[D.seg0 + s] = s < found ? s_key[s] : 0;
+    }
+  } else if (precision) {  // overflow: which starts reached the table is not defined
+    for (uint32_t s = tid; s < S; s += JIXG_T) A.starts_out[D.seg0 + s] = 0;
+  }
+  __syncthreads();
+  for (uint32_t base = 0; base < n; base += JIXG_T) {  // whole waves: the ballots below
+    const uint32_t i = base + tid;
+    const bool valid = i < n;
+    uint32_t seg = 0xffffffffu;
+    bool time_error = false, closed = false, dup = false;
+    if (valid) {
+      if (!precision) {
+        seg = 0;
+      } else {
+        unsigned long long start;
+        time_error = !jix_start(times[i], precision, &start);
+        if (!time_error && !overflow) {
+          uint32_t lo = 0, hi = found;  // the first s with s_key[s] >= start
+          while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_key[mid] < start) lo = mid + 1;
+            else hi = mid;
+          }
+          if (lo < found && lo < S && s_key[lo] == start) {
+            seg = lo;
+            closed = s_closed[lo] != 0;
+          }
+        }
+      }
+      const uint4 id = jix_id(ids, i);
+      uint32_t h = jix_hash_id(id) & imask;
+      for (uint32_t p = 0; p <= imask; p++) {
+        const uint32_t j = s_slot[h];
+        if (j == i || j == JIX_NO_INDEX) break;
+        if (jix_same(jix_id(ids, j < n ? j : i), id)) {
+          dup = true;  // the slot holds the ID's lowest index, and it is not this report
+          break;
+        }
+        h = (h + 1) & imask;
+      }
+      const uint32_t c = D.c0 + i;
+      const bool acc = seg != 0xffffffffu && !closed;
+      A.gseg[c] = seg != 0xffffffffu ? D.seg0 + seg : 0xffffffffu;
+      A.gaccept[c] = acc && A.accept[c] != 0;
+      A.seg_out[c] = seg;
+      A.rej_out[c] = closed ? PRIO3_REJECT_BATCH_COLLECTED : 0;
+      A.dup_out[c] = dup;
+    }
+    const unsigned long long m_dup = __ballot(dup), m_closed = __ballot(closed),
+                             m_err = __ballot(time_error);
+    if ((tid & 63u) == 0) {
+      if (m_dup) {
+        atomicAdd(&s_dup, (uint32_t)__popcll(m_dup));
+        atomicMin(&s_first, i + (uint32_t)(__ffsll((long long)m_dup) - 1));
+      }
+      if (m_closed) atomicAdd(&s_nclosed, (uint32_t)__popcll(m_closed));
+      if (m_err) atomicAdd(&s_err, (uint32_t)__popcll(m_err));
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    prio3_job_index_info info;
+    info.n_segments = overflow ? S + 1 : found;
+    info.overflow = overflow ? 1u : 0u;
+    info.n_duplicates = s_dup;
+    info.first_duplicate = s_first;
+    info.n_closed = s_nclosed;
+    info.n_time_errors = s_err;
+    A.info_out[blockIdx.x] = info;
+  }
+}
+
 uint32_t next_pow2(uint64_t v) {
   uint64_t p = 1;
   while (p < v) p <<= 1;
@@ -430,6 +632,15 @@ int prio3_device_job_index(prio3_engine* e, uint32_t n, const uint8_t* d_report_
   }();
   ws_release(sl, st);
   return rc;
+}
+
+int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st) {
+  static_assert(JIX_GROUP_MAX_N == PRIO3_JOB_GROUP_MAX_REPORTS &&
+                    JIX_GROUP_MAX_SEG == PRIO3_JOB_GROUP_MAX_SEGMENTS,
+                "the header's limits are the kernel's");
+  if (!n_jobs) return PRIO3_OK;
+  TIMED(e, st, "k_jix_group", (k_jix_group<<<n_jobs, JIXG_T, 0, st>>>(a)));
+  return PRIO3_OK;
 }
 
 int prio3_job_index(prio3_engine* e, uint32_t n, const uint8_t* report_ids, const uint64_t* times,

@@ -144,6 +144,21 @@ struct ExecJob {
   // 0x80 | ReportTooEarly (aggregator.rs:2004-2015) unless the open rejected it
   janus_hpke_opener* fallback = nullptr;
   uint64_t deadline = UINT64_MAX;  // seconds; UINT64_MAX: no check
+  // prio3_helper_aggregate_job: the group's launch makes the job's index itself (k_jix_group, in
+  // front of the open) -- `seg` is not read, `accept` is the host's replay mask, nseg is the job's
+  // max_segments -- and its batch metadata behind the accumulate
+  bool jix = false;
+  uint64_t precision = 0;            // time_precision (0: a fixed-size task)
+  const uint64_t* closed = nullptr;  // host [nclosed][2] (start, duration), read by stage()
+  uint32_t nclosed = 0;
+  uint32_t* jseg_out = nullptr;      // host outputs of the index: [n] job-local segment ids,
+  uint64_t* jstarts_out = nullptr;   // [nseg] (nullable), [n] reject / duplicate (nullable), info
+  uint8_t *jrej_out = nullptr, *jdup_out = nullptr;
+  void* jinfo_out = nullptr;         // prio3_job_index_info
+  uint8_t* ck_out = nullptr;         // host [nseg][32] (nullable)
+  uint64_t* iv_out = nullptr;        // host [nseg][2] (nullable)
+  uint32_t jslot = 0;    // the job's descriptor in its group
+  uint32_t closed0 = 0;  // its first row of the group's closed-interval table
   // results
   int rc = 0;
   Run* run = nullptr;  // holds one reference for this job
@@ -193,8 +208,26 @@ struct IoLayout {
   uint32_t nenc = 0, ct_stride = 0;  // ct_stride > 0: a sealed-input group
   size_t enc_off = 0, ct_off = 0, ctlen_off = 0, time_off = 0, tslot_off = 0, ttab_off = 0;
   size_t dtab_off = 0;
+  // groups of jobs that carry an index request (ExecJob::jix): the descriptor table [max_seg]
+  // (JixJobDesc; a job takes at least one segment), the closed-interval table
+  // [JIX_GROUP_CLOSED][2], and the outputs k_jix_group and the metadata launch leave: per report
+  // the job-local segment id (u32), reject and duplicate bytes; per group segment the start (u64),
+  // checksum [32] and interval [2] (u64); per job the info struct (6 x u32)
+  bool jix = false;
+  size_t jdesc_off = 0, jclosed_off = 0, jseg_off = 0, jrej_off = 0, jdup_off = 0;
+  size_t jstart_off = 0, jinfo_off = 0, ck_off = 0, iv_off = 0;
   size_t bytes;
 };
+// One job of a k_jix_group launch (read from the mapped staging).  The job's workgroup also
+// writes the pad columns [pad0, c0) and [c0 + n, end) (out-of-range segment id, not accepted).
+struct JixJobDesc {
+  uint32_t c0, n, pad0, end;
+  uint32_t seg0, max_segments, closed0, k;
+  unsigned long long precision;
+};
+constexpr uint32_t JIX_GROUP_CLOSED = 4096;  // closed intervals one group's table holds
+// the limits of the in-group path (PRIO3_JOB_GROUP_MAX_REPORTS / _SEGMENTS of janus_prio3.h)
+constexpr uint32_t JIX_GROUP_MAX_N = 4096, JIX_GROUP_MAX_SEG = 64;
 // job: the group's first job (its opener and ciphertext stride shape a sealed-input group)
 void engine_io_layout(const prio3_engine* e, uint32_t cap, IoLayout* L,
                       const ExecJob* job = nullptr);
@@ -212,6 +245,7 @@ struct GroupView {
   int require_taskprov = 0;
   janus_hpke_opener* fallback = nullptr;  // the keypair its HpkeDecryptError reports are retried with
   bool deadlines = false;  // some job of the group carries a report deadline
+  uint32_t njix = 0;       // jobs with an index request (then every job of the group is one)
 };
 // segments one group can aggregate (its aggregating jobs' n_segments summed)
 constexpr uint32_t EXEC_MAX_SEGS = 1024;

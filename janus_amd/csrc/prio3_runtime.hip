@@ -1007,6 +1007,7 @@ struct PrepPolicy {
     int require_taskprov = 0;
     bool any_deadline = false;
     uint32_t n = 0, cap = 0, jobs = 0, nseg = 0, align = 1;
+    uint32_t njix = 0, nclosed = 0;  // index requests and the rows of their closed-interval table
     IoLayout L;
     Run* run = nullptr;
   };
@@ -1045,6 +1046,14 @@ struct PrepPolicy {
     if (c0 + j->n > s.cap || ((c0 + j->n + 63) & ~63u) > s.cap ||
         s.nseg + j->nseg > s.L.max_seg)
       return false;
+    // an index request: a descriptor (one per job, and a job takes a segment: njix <= max_seg) and
+    // room for its closed intervals in the group's table
+    if (j->jix && (!s.L.jix || s.nclosed + j->nclosed > JIX_GROUP_CLOSED)) return false;
+    if (j->jix) {
+      j->jslot = s.njix++;
+      j->closed0 = s.nclosed;
+      s.nclosed += j->nclosed;
+    }
     if (k == s.keys.size()) s.keys.push_back(j->e);
     if (j->opener && t == s.tasks.size()) {
       std::array<uint8_t, 32> id;
@@ -1104,7 +1113,27 @@ struct PrepPolicy {
     // stays out of every aggregate: 0xFFFFFFFF); a prepare-only job's reports are out
     uint32_t* sg = (uint32_t*)(g.p + L.seg_off) + j->c0;
     uint8_t* ac = g.p + L.accept_off + j->c0;
-    if (j->nseg == 0) {
+    if (j->jix) {
+      // the launch makes the segment ids (k_jix_group); the accept bytes are the host's mask, and
+      // the job's descriptor and closed intervals are read here, before the call returns
+      if (j->accept)
+        memcpy(ac, j->accept, j->n);
+      else
+        memset(ac, 1, j->n);
+      JixJobDesc d;
+      d.c0 = j->c0;
+      d.n = j->n;
+      d.pad0 = j->pad0;
+      d.end = j->c0 + j->n;
+      d.seg0 = j->seg0;
+      d.max_segments = j->nseg;
+      d.closed0 = j->closed0;
+      d.k = j->precision ? j->nclosed : 0;
+      d.precision = j->precision;
+      memcpy(g.p + L.jdesc_off + sizeof(JixJobDesc) * j->jslot, &d, sizeof d);
+      if (j->nclosed)
+        memcpy(g.p + L.jclosed_off + 16 * (size_t)j->closed0, j->closed, 16 * (size_t)j->nclosed);
+    } else if (j->nseg == 0) {
       for (uint32_t i = 0; i < j->n; i++) sg[i] = 0xFFFFFFFFu;
       memset(ac, 0, j->n);
     } else {
@@ -1130,6 +1159,10 @@ struct PrepPolicy {
       pad(s.L, g, s.n, n1);
       s.n = n1;
     }
+    // the last job's workgroup also writes the tail pad's segment ids and accept bytes
+    if (s.njix)
+      ((JixJobDesc*)(g.p + s.L.jdesc_off))[s.njix - 1].end = s.n;
+    v.njix = s.njix;
     v.n = s.n;
     v.cap = s.cap;
     v.stg = g.p;
@@ -1156,6 +1189,19 @@ struct PrepPolicy {
     if (j->nseg) {
       memcpy(j->agg_out, g.p + L.agg_off + L.agg_len * j->seg0, L.agg_len * j->nseg);
       memcpy(j->counts_out, g.p + L.cnt_off + 8 * (size_t)j->seg0, 8 * (size_t)j->nseg);
+    }
+    if (j->jix) {
+      const size_t c0 = j->c0, n = j->n, s0 = j->seg0, S = j->nseg;
+      memcpy(j->jseg_out, g.p + L.jseg_off + 4 * c0, 4 * n);
+      if (j->jrej_out) memcpy(j->jrej_out, g.p + L.jrej_off + c0, n);
+      if (j->jdup_out) memcpy(j->jdup_out, g.p + L.jdup_off + c0, n);
+      // a fixed-size task has no starts: the caller's array is left as it is (prio3_job_index)
+      if (j->jstarts_out && j->precision)
+        memcpy(j->jstarts_out, g.p + L.jstart_off + 8 * s0, 8 * S);
+      memcpy(j->jinfo_out, g.p + L.jinfo_off + sizeof(prio3_job_index_info) * j->jslot,
+             sizeof(prio3_job_index_info));
+      if (j->ck_out) memcpy(j->ck_out, g.p + L.ck_off + 32 * s0, 32 * S);
+      if (j->iv_out) memcpy(j->iv_out, g.p + L.iv_off + 16 * s0, 16 * S);
     }
     j->run = s.run;  // one reference per job (engine_group_finish sets refs = jobs)
   }

@@ -105,6 +105,31 @@ class Prio3JobIndexInfo(C.Structure):
 #: d_reject of a report in a closed batch: 0x80 | PrepareError::BatchCollected
 REJECT_BATCH_COLLECTED = 0x80
 
+#: the limits of prio3_helper_aggregate_job's in-group path (PRIO3_JOB_GROUP_MAX_REPORTS /
+#: PRIO3_JOB_GROUP_MAX_SEGMENTS); a larger job runs the three calls inside the entry point
+JOB_GROUP_MAX_REPORTS = 4096
+JOB_GROUP_MAX_SEGMENTS = 64
+
+
+class Prio3HelperJobIn(C.Structure):
+    """prio3_helper_job_in (include/janus_prio3.h)."""
+    _fields_ = [("opener", C.c_void_p), ("fallback_opener", C.c_void_p),
+                ("report_deadline", C.c_uint64), ("n", C.c_uint32),
+                ("require_taskprov", C.c_int32), ("task_id", C.c_void_p),
+                ("report_ids", C.c_void_p), ("times", C.c_void_p), ("public_shares", C.c_void_p),
+                ("enc", C.c_void_p), ("ct", C.c_void_p), ("ct_len", C.c_void_p),
+                ("leader_prep_shares", C.c_void_p), ("ct_stride", C.c_uint32), ("k", C.c_uint32),
+                ("time_precision", C.c_uint64), ("closed_intervals", C.c_void_p),
+                ("accept_mask", C.c_void_p), ("max_segments", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class Prio3HelperJobOut(C.Structure):
+    """prio3_helper_job_out (include/janus_prio3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "segment_ids", "segment_starts", "reject", "duplicate", "info", "prep_msgs", "status",
+        "agg_shares", "counts", "checksums", "intervals")]
+
 #: Every symbol include/janus_prio3.h declares.
 EXPORTED_SYMBOLS = (
     "prio3_sizes", "prio3_engine_create", "prio3_engine_destroy", "prio3_helper_prepare_batch",
@@ -125,7 +150,7 @@ EXPORTED_SYMBOLS = (
     "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
     "prio3_client_rand_len", "prio3_client_report_stride", "prio3_selftest_tile",
     "prio3_device_leader_upload", "prio3_leader_upload_batch",
-    "prio3_device_job_index", "prio3_job_index",
+    "prio3_device_job_index", "prio3_job_index", "prio3_helper_aggregate_job",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -183,6 +208,7 @@ def load_library() -> C.CDLL:
     L.prio3_helper_aggregate_init_batch_ex.argtypes = [vp, vp, vp, C.c_uint64, u32, vp, C.c_int, vp,
                                                        vp, vp, vp, vp, vp, u32, vp, vp, vp, u32,
                                                        vp, vp, vp, vp]
+    L.prio3_helper_aggregate_job.argtypes = [vp, P(Prio3HelperJobIn), P(Prio3HelperJobOut)]
     L.prio3_debug_output_shares.argtypes = [vp, vp]
     L.prio3_batch_free.argtypes = [vp]
     L.prio3_batch_free.restype = None
@@ -623,6 +649,77 @@ class HelperEngine:
         if rc:
             raise RuntimeError(f"prio3_helper_aggregate_init_batch failed (rc={rc})")
         return msgs[:, :sz.prep_msg_len], status, agg, cnt
+
+    def aggregate_job(self, opener, task_id: bytes, report_ids, times, public_shares, enc, ct,
+                      ct_len, leader_prep_shares, time_precision: int, max_segments: int,
+                      closed_intervals=None, accept_mask=None, require_taskprov=False,
+                      fallback_opener=None, report_deadline=None) -> dict:
+        """A whole helper aggregation job in one call (prio3_helper_aggregate_job): the job index
+        (``job_index``), the loop body (``aggregate_init_batch`` with fallback keypair and report
+        deadline) over the index's segment ids and its accept bytes ANDed with ``accept_mask``, and
+        the batch metadata (``batch_metadata``), byte for byte what the three calls give.  Returns
+        a dict: segment_ids [n], segment_starts [S], reject [n], duplicate [n], the fields of
+        Prio3JobIndexInfo, prep_msgs, status [n], agg [S, agg_len], counts [S], checksums [S, 32]
+        and intervals [S, 2], with S = max_segments."""
+        sz = self.sz
+        ids = np.ascontiguousarray(report_ids, np.uint8).reshape(-1, 16)
+        n = ids.shape[0]
+        t = np.ascontiguousarray(times, np.uint64)
+        e = np.ascontiguousarray(enc, np.uint8)
+        c = np.ascontiguousarray(ct, np.uint8)
+        cl = np.ascontiguousarray(ct_len, np.uint32)
+        lps = np.ascontiguousarray(leader_prep_shares, np.uint8)
+        if t.shape != (n,) or cl.shape != (n,) or c.ndim != 2 or c.shape[0] != n or \
+                e.shape[0] != n or lps.shape != (n, sz.prep_share_len):
+            raise ValueError("input shapes do not match the job")
+        if len(task_id) != 32:
+            raise ValueError("task_id must be 32 bytes")
+        pub = None
+        if sz.public_share_len:
+            pub = np.ascontiguousarray(public_shares, np.uint8)
+            if pub.shape != (n, sz.public_share_len):
+                raise ValueError("public share shape does not match the VDAF instance")
+        m = None
+        if accept_mask is not None:
+            m = np.ascontiguousarray(accept_mask, np.uint8)
+            if m.shape != (n,):
+                raise ValueError("accept_mask must have one byte per report")
+        cz, k = self._closed(closed_intervals)
+        S = max(0, min(int(max_segments), 4096))
+        tid = (C.c_uint8 * 32).from_buffer_copy(task_id)
+        seg = np.zeros(n, np.uint32)
+        starts = np.zeros(S, np.uint64)
+        rej = np.zeros(n, np.uint8)
+        dup = np.zeros(n, np.uint8)
+        info = Prio3JobIndexInfo()
+        msgs = np.zeros((n, max(sz.prep_msg_len, 1)), np.uint8)
+        status = np.zeros(n, np.uint8)
+        agg = np.zeros((S, sz.agg_share_len), np.uint8)
+        cnt = np.zeros(S, np.uint64)
+        ck = np.zeros((S, 32), np.uint8)
+        iv = np.zeros((S, 2), np.uint64)
+        a = lambda x: None if x is None else x.ctypes.data
+        jin = Prio3HelperJobIn(
+            opener=None if opener is None else opener.handle.value,
+            fallback_opener=None if fallback_opener is None else fallback_opener.handle.value,
+            report_deadline=(1 << 64) - 1 if report_deadline is None else int(report_deadline),
+            n=n, require_taskprov=int(bool(require_taskprov)), task_id=C.addressof(tid),
+            report_ids=a(ids), times=a(t), public_shares=a(pub), enc=a(e), ct=a(c), ct_len=a(cl),
+            leader_prep_shares=a(lps), ct_stride=c.shape[1], k=k,
+            time_precision=int(time_precision), closed_intervals=a(cz), accept_mask=a(m),
+            max_segments=int(max_segments), reserved=0)
+        jout = Prio3HelperJobOut(
+            segment_ids=a(seg), segment_starts=a(starts), reject=a(rej), duplicate=a(dup),
+            info=C.addressof(info), prep_msgs=a(msgs), status=a(status), agg_shares=a(agg),
+            counts=a(cnt), checksums=a(ck), intervals=a(iv))
+        rc = load_library().prio3_helper_aggregate_job(self.handle, C.byref(jin), C.byref(jout))
+        if rc:
+            raise RuntimeError(f"prio3_helper_aggregate_job failed (rc={rc})")
+        out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
+                   prep_msgs=msgs[:, :sz.prep_msg_len], status=status, agg=agg, counts=cnt,
+                   checksums=ck, intervals=iv)
+        out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
+        return out
 
     # ---- leader side (same instance, agg_id 0) -----------------------------------
     def leader_prepare_init_batch(self, nonces, public_shares, leader_input_shares):

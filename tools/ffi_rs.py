@@ -84,6 +84,7 @@ def parse_header(path: str) -> dict:
             decl = " ".join(decl.split())
             if not decl:
                 continue
+            decl = re.sub(r"\bstruct\s+", "", decl)  # a field `struct T* x` (an opaque handle)
             tm = re.match(r"^((?:const\s+)?[\w]+\s*\**)\s*(.*)$", decl)
             ctype, names = tm.group(1).strip(), tm.group(2)
             for nm in names.split(","):
