@@ -673,7 +673,8 @@ int prio3_device_trim(int device);
 /* force_slow_path=1 routes every report through the general rejection-sampling kernel;
  * leader_fuse_acc=0 turns off the fused device-leader accumulate (A/B); pair_max=N runs
  * Histogram(P = 32) prepares of at most N reports on lane pairs (0: never); the other keys are
- * the launch variants prio3_engine_set_option (prio3_engine.hip) lists. */
+ * the launch variants prio3_engine_set_option (prio3_engine.hip) lists.  test_reject_bits=N
+ * (0..24) exists only in the test-rejection build (libjanus_prio3_rej.so); elsewhere it fails. */
 int prio3_engine_set_option(prio3_engine* engine, const char* key, int64_t value);
 /* Per-kernel device time (ms) accumulated since the last reset, measured with HIP events
  * on the launch stream when option "timing" is 1 (2: launches counted, no events or times).
@@ -692,6 +693,17 @@ int prio3_trace_enabled(void);
  * 4/5: sum of 16 products per output through the lazily reduced MAC (a, b hold 16 n elements).
  * Lets tests pin the hand-written asm arithmetic against Python integers directly. */
 int prio3_selftest_field(int op, uint32_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
+
+/* Test-only: Field64 primitives and the limit-operand pieces of Field128, one result per i < n.
+ * op 0/1/2: a*b, a+b, a-b in Field64 (8-byte LE a, b, out);  3: the reduction of the raw 128-bit
+ * value lo = a[i], hi = b[i];  4: sum of k products per output through the lazily reduced Field64
+ * MAC (a, b hold k n elements);  5: 1 if the raw a[i] < p64, else 0;  6: the same for a raw
+ * 16-byte a[i] and p128 (8-byte out);  7: a[i] added k times through the lazy Field128 sum, then
+ * reduced (16-byte a, out; b unused from op 5 on);  8: the measurement-share truncation with
+ * nb = k <= 32 over two entries: a holds 2 k n 16-byte elements (lane i's at 2 k i), out the
+ * entries as [2][n] 16-byte elements. */
+int prio3_selftest_field64(int op, uint32_t n, uint32_t k, const uint8_t* a, const uint8_t* b,
+                           uint8_t* out);
 
 /* Test-only: runs the fused accumulate's tile reduction on one wave's host-supplied values.
  * values: [8][64][16 B], slot-major (slot s of lane l at (s * 64 + l) * 16, LE Field128 words);

@@ -481,7 +481,7 @@ DEV void shard_report(const DevParams& p, const GenScratch& gs, const ShardIn& i
   auto expand = [&](const uint32_t* dst2, const uint32_t* seed, const uint8_t* binder, int blen,
                     uint32_t n, void* base) {
     if constexpr (SLOW)
-      bx_expand<F>(dst2, seed, binder, blen, n, base, ld, c);
+      bx_expand<F>(p, dst2, seed, binder, blen, n, base, ld, c);
     else
       expand_to<F>(p, dst2, seed, binder, blen, n, base, c, flag);
   };
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(64) void k_fg_shares(DevParams p, uint64_t seed, ui
     for (uint32_t b = 0; b < K; b++) {
       squeeze_block_with<F>(s, b, M, q0, q1, [&](uint32_t i, const uint32_t* w) {
         const T h = F::from_words(w);
-        if (!F::lt_p(h)) flag = 1;
+        if (!F::accept(h, REJ_BITS(p))) flag = 1;
         const T l = F::sub(F::from_u32(fg_mbit(p, X, N, i)), h);
         F::store(lin, i, l);
         if (i < nb * Ln) {
@@ -926,7 +926,7 @@ __global__ __launch_bounds__(64) void k_fg_finish(DevParams p, GenOut go, FgBufs
   for (uint32_t b = 0; b < K; b++) {
     squeeze_block_with<F>(s, b, PL, q0, q1, [&](uint32_t i, const uint32_t* w) {
       const f128 h = F::from_words(w);
-      if (!F::lt_p(h)) flag = 1;
+      if (!F::accept(h, REJ_BITS(p))) flag = 1;
       F::store(lp, i, F::sub(F::load(prf, i), h));
     });
     if (b + 1 < K) keccak_p12(s);
@@ -1238,11 +1238,11 @@ __global__ __launch_bounds__(64) void k_leader_init(DevParams p, const uint8_t* 
     uint8_t b[17];
     b[0] = 1;
     for (int i = 0; i < 16; i++) b[1 + i] = (uint8_t)(nonce[i >> 2] >> (8 * (i & 3)));
-    bx_expand<F>(p.dst[5], vk, b, 17, 1, sc.qr, ld, r);
+    bx_expand<F>(p, p.dst[5], vk, b, 17, 1, sc.qr, ld, r);
     if (JR) {
       const uint4 c = sc.corrected[r];
       const uint32_t cor[4] = {c.x, c.y, c.z, c.w};
-      bx_expand<F>(p.dst[3], cor, b, 1, p.jr_len, sc.jr, ld, r);
+      bx_expand<F>(p, p.dst[3], cor, b, 1, p.jr_len, sc.jr, ld, r);
     }
   }
   const T t = F::load(sc.qr, r);

@@ -65,7 +65,20 @@ struct DevParams {
   // Prio3Sum query (k_query_sum, P = 16 NPH): tws[j] = w16^j (j < 8), tws[8 + i] = alpha_P^i
   // (i < 8), tws[16 + i] = alpha_P^(16 i) (i < 8)
   uint32_t tws[24][4];
+#ifdef JANUS_TEST_REJECT
+  uint32_t test_reject;  // F::accept's bits (engine option test_reject_bits)
+#endif
 };
+// the sampler's extra-rejection bits of the test-rejection build (prio3_device.h F::accept)
+#ifdef JANUS_TEST_REJECT
+#define REJ_BITS(p) ((p).test_reject)
+#define BX_REJ(x) ((x).rej)
+#define BX_SET_REJ(x, p) ((x).rej = (p).test_reject)
+#else
+#define REJ_BITS(p) 0u
+#define BX_REJ(x) 0u
+#define BX_SET_REJ(x, p) ((void)0)
+#endif
 
 struct InPtrs {
   const uint8_t* nonces;
@@ -187,6 +200,9 @@ struct BX {
   KState s;
   uint8_t buf[168];
   uint32_t pos;
+#ifdef JANUS_TEST_REJECT
+  uint32_t rej = 0;  // BX_SET_REJ
+#endif
 };
 DEV void bx_xor_block(BX& x) {
 #pragma unroll
@@ -248,15 +264,17 @@ DEV void bx_next_elem(BX& x, uint32_t* w) {
       for (int b = 0; b < 4; b++) v |= (uint32_t)bx_squeeze(x) << (8 * b);
       w[k] = v;
     }
-    if (F::lt_p(F::from_words(w))) return;
+    if (F::accept(F::from_words(w), BX_REJ(x))) return;
   }
 }
 
 // XOF(seed, dst, binder).expand_into_vec(n) with rejection sampling, into SoA columns
 template <class F>
-DEV void bx_expand(const uint32_t* dst2, const uint32_t* seed, const uint8_t* binder, int blen,
-                   uint32_t n, void* base, size_t ld, uint32_t r) {
+DEV void bx_expand(const DevParams& p, const uint32_t* dst2, const uint32_t* seed,
+                   const uint8_t* binder, int blen, uint32_t n, void* base, size_t ld,
+                   uint32_t r) {
   BX x;
+  BX_SET_REJ(x, p);
   bx_init(x, dst2, seed);
   for (int i = 0; i < blen; i++) bx_absorb(x, binder[i]);
   bx_finalize(x);
@@ -274,7 +292,7 @@ template <class F>
 DEV void put_elem(const DevParams& p, void* base, uint32_t idx, uint32_t r, const uint32_t* w,
                   uint32_t& flag) {
   typename F::T x = F::from_words(w);
-  if (!F::lt_p(x)) flag = 1;
+  if (!F::accept(x, REJ_BITS(p))) flag = 1;
   DCHECK(r < p.ld);
   F::store(base, (size_t)idx * p.ld + r, x);
 }

@@ -526,6 +526,18 @@ DEV uint64_t mac64_reduce(const mac64& a) {
 // -------------------------------------------------------------------------------------
 // Generic field traits so kernels can be templated on the field.
 // -------------------------------------------------------------------------------------
+// Test-rejection build (make -C janus_amd REJECT_TEST=1 -> libjanus_prio3_rej.so): the samplers'
+// acceptance test F::accept(x, bits) also rejects a candidate whose top `bits` bits (of the
+// little-endian value; 1..24, 0 = off) are all ones.  The top 32 bits of both moduli are ones, so
+// that is a superset of what prio rejects: accepted values stay canonical and the rejection paths
+// run at a rate 2^-bits instead of 2^-32 (Field64) / 2^-59 (Field128).  Compiled out of the
+// product library, where accept is lt_p and nothing else.
+#ifdef JANUS_TEST_REJECT
+DEV bool top_ones(uint32_t top_word, uint32_t bits) {
+  return bits != 0 && (top_word >> (32 - bits)) == (0xffffffffu >> (32 - bits));
+}
+#endif
+
 struct Fp128 {
   typedef f128 T;
   static constexpr int ES = 16;
@@ -541,6 +553,12 @@ struct Fp128 {
   static DEV bool eq(const T& a, const T& b) { return eq128(a, b); }
   static DEV bool is_zero(const T& a) { return is_zero128(a); }
   static DEV bool lt_p(const T& a) { return !ge_p128(a); }
+  // the acceptance test of rejection *sampling* (decode checks keep lt_p)
+#ifdef JANUS_TEST_REJECT
+  static DEV bool accept(const T& a, uint32_t bits) { return lt_p(a) && !top_ones(a.w[3], bits); }
+#else
+  static DEV bool accept(const T& a, uint32_t) { return lt_p(a); }
+#endif
   static DEV T sel(bool c, const T& a, const T& b) { return sel128(c, a, b); }
   static DEV T from_words(const uint32_t* w) { return mk128(w[0], w[1], w[2], w[3]); }
   static DEV T from_u32(uint32_t x) { return mk128(x, 0, 0, 0); }
@@ -564,6 +582,11 @@ struct Fp64 {
   static DEV bool eq(T a, T b) { return a == b; }
   static DEV bool is_zero(T a) { return a == 0; }
   static DEV bool lt_p(T a) { return a < P64; }
+#ifdef JANUS_TEST_REJECT
+  static DEV bool accept(T a, uint32_t bits) { return lt_p(a) && !top_ones((uint32_t)(a >> 32), bits); }
+#else
+  static DEV bool accept(T a, uint32_t) { return lt_p(a); }
+#endif
   static DEV T sel(bool c, T a, T b) { return c ? a : b; }
   static DEV T from_words(const uint32_t* w) { return (uint64_t)w[1] << 32 | w[0]; }
   static DEV T from_u32(uint32_t x) { return x; }

@@ -73,6 +73,42 @@ __global__ void k_selftest_f128(int op, uint32_t n, const uint4* a, const uint4*
   out[i] = make_uint4(z.w[0], z.w[1], z.w[2], z.w[3]);
 }
 
+// Field64 primitives and the limit-operand pieces of Field128 (prio3_selftest_field64):
+// op 0/1/2: mul64f / add64f / sub64f of a[i], b[i];  3: red128_64(lo = a[i], hi = b[i]);
+// op 4: sum_{j<k} a_(k i+j) b_(k i+j) via mac64_add + mac64_reduce;  5: Fp64::lt_p(a[i]);
+// op 6: Fp128::lt_p(a[i]) (16-byte a);  7: sum_reduce of k sum_add of a[i] (16-byte a and out);
+// op 8: TruncSink with nb = k over two entries, elements a_(2 k i ..) -> out[e * n + i] (16-byte).
+__global__ void k_selftest_f64(int op, uint32_t n, uint32_t k, const uint64_t* a, const uint64_t* b,
+                               uint64_t* out, DevParams p) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  auto ld = [](const uint64_t* q, size_t j) {
+    const uint4 v = ((const uint4*)q)[j];
+    return mk128(v.x, v.y, v.z, v.w);
+  };
+  if (op == 0) out[i] = mul64f(a[i], b[i]);
+  else if (op == 1) out[i] = add64f(a[i], b[i]);
+  else if (op == 2) out[i] = sub64f(a[i], b[i]);
+  else if (op == 3) out[i] = red128_64(a[i], b[i]);
+  else if (op == 4) {
+    mac64 m;
+    mac64_zero(m);
+    for (uint32_t j = 0; j < k; j++) mac64_add(m, a[(size_t)i * k + j], b[(size_t)i * k + j]);
+    out[i] = mac64_reduce(m);
+  } else if (op == 5) out[i] = Fp64::lt_p(a[i]) ? 1 : 0;
+  else if (op == 6) out[i] = Fp128::lt_p(ld(a, i)) ? 1 : 0;
+  else if (op == 7) {
+    sum128 sm;
+    sum_zero(sm);
+    const f128 x = ld(a, i);
+    for (uint32_t j = 0; j < k; j++) sum_add(sm, x);
+    Fp128::store(out, i, sum_reduce(sm));
+  } else {
+    TruncSink ts(p, out, i);
+    for (uint32_t j = 0; j < 2 * k; j++) ts.put(ld(a, (size_t)i * 2 * k + j));
+  }
+}
+
 // The fused accumulate's tile reduction (tile_stage / tile_halfsum) on caller-supplied values:
 // one wave stages all FTILE slots from in [FTILE][64][16 B] (slot, lane) and writes the 8 addends
 // of the first cnt slots to out [cnt][8]; the slots from cnt on are staged too and must not count.
@@ -1461,6 +1497,14 @@ int prio3_engine_set_option(prio3_engine* e, const char* key, int64_t value) {
       *o.field = (int)value;
       return PRIO3_OK;
     }
+#ifdef JANUS_TEST_REJECT
+  // test-rejection build only: the samplers also reject candidates whose top `value` bits are ones
+  if (!strcmp(key, "test_reject_bits")) {
+    if (value < 0 || value > 24) return PRIO3_EINVAL;
+    e->dp.test_reject = (uint32_t)value;
+    return PRIO3_OK;
+  }
+#endif
   if (!strcmp(key, "fp_sub_bytes")) {  // FPVec scratch budget per sub-batch (0 = auto)
     if (value < 0) return PRIO3_EINVAL;
     e->fp_sub_bytes = value;
@@ -2374,6 +2418,40 @@ int prio3_selftest_field(int op, uint32_t n, const uint8_t* a, const uint8_t* b,
     k_selftest_f128<<<(n + 255) / 256, 256>>>(op, n, (const uint4*)da, (const uint4*)db, (uint4*)dout);
     if (hipGetLastError() != hipSuccess ||
         hipMemcpy(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = PRIO3_EDEVICE;
+  }
+  (void)hipFree(da);
+  (void)hipFree(db);
+  (void)hipFree(dout);
+  return rc;
+}
+
+int prio3_selftest_field64(int op, uint32_t n, uint32_t k, const uint8_t* a, const uint8_t* b,
+                           uint8_t* out) {
+  if (op < 0 || op > 8 || !a || !out) return PRIO3_EINVAL;
+  if ((op == 4 || op == 7) && k == 0) return PRIO3_EINVAL;
+  if (op == 8 && (k == 0 || k > 32)) return PRIO3_EINVAL;
+  if (op <= 4 && !b) return PRIO3_EINVAL;
+  if (n == 0) return PRIO3_OK;
+  const size_t per = op == 4 ? k : op == 8 ? 2 * (size_t)k : 1, es = op >= 6 ? 16 : 8;
+  const size_t ma = per * n * es, mb = op <= 4 ? ma : 0;
+  const size_t mo = (size_t)n * (op == 7 ? 16 : op == 8 ? 32 : 8);
+  DevParams p{};
+  p.ld_out = n;
+  p.bits = k;
+  p.out_len = 2;
+  void *da = nullptr, *db = nullptr, *dout = nullptr;
+  int rc = PRIO3_OK;
+  if (hipMalloc(&da, ma) != hipSuccess || (mb && hipMalloc(&db, mb) != hipSuccess) ||
+      hipMalloc(&dout, mo) != hipSuccess ||
+      hipMemcpy(da, a, ma, hipMemcpyHostToDevice) != hipSuccess ||
+      (mb && hipMemcpy(db, b, mb, hipMemcpyHostToDevice) != hipSuccess)) {
+    rc = PRIO3_EDEVICE;
+  } else {
+    k_selftest_f64<<<(n + 255) / 256, 256>>>(op, n, k, (const uint64_t*)da, (const uint64_t*)db,
+                                             (uint64_t*)dout, p);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(out, dout, mo, hipMemcpyDeviceToHost) != hipSuccess)
       rc = PRIO3_EDEVICE;
   }
   (void)hipFree(da);

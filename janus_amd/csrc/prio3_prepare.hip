@@ -1051,10 +1051,10 @@ __global__ __launch_bounds__(64) void k_leader_slowfix(DevParams p, InPtrs in, S
   for (int i = 0; i < 16; i++) b[1 + i] = (uint8_t)(nonce[i >> 2] >> (8 * (i & 3)));
   uint32_t vk[4];
   load_vk(p, in, r, vk);
-  bx_expand<F>(p.dst[5], vk, b, 17, p.qr_len, sc.qr, p.ld, r);
+  bx_expand<F>(p, p.dst[5], vk, b, 17, p.qr_len, sc.qr, p.ld, r);
   const uint4 c = sc.corrected[r];
   const uint32_t cor[4] = {c.x, c.y, c.z, c.w};
-  bx_expand<F>(p.dst[3], cor, b, 1, p.jr_len, sc.jr, p.ld, r);
+  bx_expand<F>(p, p.dst[3], cor, b, 1, p.jr_len, sc.jr, p.ld, r);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1073,6 +1073,7 @@ __device__ __noinline__ void xof_slow_one(const DevParams& p, const InPtrs& in, 
   uint32_t w[4];
   {  // query rand
     BX x;
+    BX_SET_REJ(x, p);
     uint32_t vk[4];
     load_vk(p, in, r, vk);
     bx_init(x, p.dst[5], vk);
@@ -1086,6 +1087,7 @@ __device__ __noinline__ void xof_slow_one(const DevParams& p, const InPtrs& in, 
   }
   {  // measurement share
     BX x;
+    BX_SET_REJ(x, p);
     uint32_t km[4];
     load16(hs, km);
     bx_init(x, p.dst[1], km);
@@ -1131,6 +1133,7 @@ __device__ __noinline__ void xof_slow_one(const DevParams& p, const InPtrs& in, 
   }
   {  // proofs
     BX x;
+    BX_SET_REJ(x, p);
     uint32_t kp[4];
     load16(hs + 16, kp);
     bx_init(x, p.dst[2], kp);
@@ -1159,6 +1162,7 @@ __device__ __noinline__ void xof_slow_one(const DevParams& p, const InPtrs& in, 
       }
     }
     BX y;
+    BX_SET_REJ(y, p);
     bx_init(y, p.dst[3], cor);
     bx_absorb(y, 1);
     bx_finalize(y);

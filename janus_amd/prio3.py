@@ -149,6 +149,7 @@ EXPORTED_SYMBOLS = (
     "prio3_leader_prepare_next_aggregate_batch",
     "prio3_client_shard_device", "prio3_client_shard_batch", "prio3_client_prepare_reports_device",
     "prio3_client_rand_len", "prio3_client_report_stride", "prio3_selftest_tile",
+    "prio3_selftest_field64",
     "prio3_device_leader_upload", "prio3_leader_upload_batch",
     "prio3_device_job_index", "prio3_job_index", "prio3_helper_aggregate_job",
 )
@@ -225,6 +226,7 @@ def load_library() -> C.CDLL:
     L.prio3_engine_timing_reset.restype = None
     L.prio3_selftest_field.argtypes = [C.c_int, C.c_uint32, vp, vp, vp]
     L.prio3_selftest_tile.argtypes = [C.c_uint32, vp, vp]
+    L.prio3_selftest_field64.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.prio3_trace_enabled.argtypes = []
     L.prio3_device_trim.argtypes = [C.c_int]
     L.prio3_device_prepare_aggregate.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32,
@@ -275,6 +277,24 @@ def selftest_field(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     rc = load_library().prio3_selftest_field(op, n, _np_ptr(a), _np_ptr(b), _np_ptr(out))
     if rc:
         raise RuntimeError(f"prio3_selftest_field failed (rc={rc})")
+    return out
+
+
+def selftest_field64(op: int, n: int, k: int, a: np.ndarray,
+                     b: Optional[np.ndarray] = None) -> np.ndarray:
+    """Test hook: Field64 primitives and the limit-operand pieces of Field128 (ops of
+    prio3_selftest_field64 in the header) over uint8 operand rows; returns uint8 [n, 8]
+    (op 7: [n, 16]; op 8: [2, n, 16])."""
+    a = np.ascontiguousarray(a, np.uint8)
+    b = None if b is None else np.ascontiguousarray(b, np.uint8)
+    per = k if op == 4 else 2 * k if op == 8 else 1
+    es = 16 if op >= 6 else 8
+    assert a.size == per * n * es and (b is None or b.size == a.size)
+    out = np.zeros((2, n, 16) if op == 8 else (n, 16 if op == 7 else 8), np.uint8)
+    rc = load_library().prio3_selftest_field64(op, n, k, _np_ptr(a),
+                                               None if b is None else _np_ptr(b), _np_ptr(out))
+    if rc:
+        raise RuntimeError(f"prio3_selftest_field64 failed (rc={rc})")
     return out
 
 

@@ -67,6 +67,8 @@ def lib():
         L.orc_gen_reports.argtypes = [P(OrcParams), u8p, C.c_uint32, C.c_uint64, C.c_int,
                                       u8p, u8p, u8p, u8p, P(C.c_uint64), u8p]
         L.orc_prim_bench.argtypes = [P(C.c_double), P(C.c_double)]
+        L.orc_set_test_reject.argtypes = [C.c_int]
+        L.orc_reject_record.argtypes = [P(C.c_uint32)]
         _lib = L
     return _lib
 
@@ -81,6 +83,41 @@ def _out(n):
 
 def _ptr(a: np.ndarray, ctype=C.c_uint8):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
+
+
+REJ_STREAMS = ("query", "meas", "proofs", "jr", "prove")
+
+
+def set_test_reject(bits: int) -> None:
+    """Test-rejection predicate (default 0 = off): every sampler of the restatement also rejects a
+    candidate whose top `bits` bits are all ones, as the engine's libjanus_prio3_rej.so does with
+    option test_reject_bits.  Process-wide."""
+    lib().orc_set_test_reject(bits)
+
+
+def get_test_reject() -> int:
+    return lib().orc_get_test_reject()
+
+
+class RejectRecord:
+    """with RejectRecord() as rec: ...single-report calls...; rec.streams() -> {stream:
+    (count, [(candidate position, element index), ...up to 6])} over the calls made inside."""
+
+    def __enter__(self):
+        self.buf = np.zeros((5, 13), np.uint32)
+        lib().orc_reject_record(_ptr(self.buf, C.c_uint32))
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_reject_record(None)
+
+    def streams(self):
+        out = {}
+        for s, name in enumerate(REJ_STREAMS):
+            c = int(self.buf[s, 0])
+            out[name] = (c, [(int(self.buf[s, 1 + 2 * i]), int(self.buf[s, 2 + 2 * i]))
+                             for i in range(min(c, 6))])
+        return out
 
 
 def turboshake128(msg: bytes, domain: int, n: int) -> bytes:
@@ -206,6 +243,18 @@ class Oracle:
                                    _ptr(status), _ptr(agg), _ptr(cnt, C.c_uint64), n_threads,
                                    job_size)
         return ps, status, agg, cnt
+
+    def reject_scan(self, vk, agg_id, nonces, public_shares, shares):
+        """Per report, the rejections of every stream the aggregator (0 leader on explicit input
+        shares, 1 helper) samples in prepare_init: a list of RejectRecord.streams() dicts."""
+        out = []
+        pl = self.p.public_share_len
+        for r in range(len(nonces)):
+            with RejectRecord() as rec:
+                self.prepare_init(vk, agg_id, bytes(nonces[r]),
+                                  bytes(public_shares[r][:pl]) if pl else b"", bytes(shares[r]))
+            out.append(rec.streams())
+        return out
 
     def gen_reports(self, vk: bytes, n: int, seed: int = 1, n_threads: int = 8):
         """Deterministic honest reports: dict of uint8 arrays + measurements + leader out shares."""

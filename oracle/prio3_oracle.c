@@ -369,15 +369,47 @@ static int dec_fe(const fld* F, const uint8_t* in, fe* x) {
   return 0;
 }
 
+/* Test infrastructure (default off): with reject_bits = b (1..24) the sampler also rejects a
+ * candidate whose top b bits are all ones -- the engine's test-rejection build (F::accept).  The
+ * top 32 bits of both moduli are ones, so accepted values stay canonical.  Set it while no batch
+ * call is running. */
+static int g_reject_bits = 0;
+void orc_set_test_reject(int bits) { g_reject_bits = bits < 0 ? 0 : bits > 24 ? 24 : bits; }
+int orc_get_test_reject(void) { return g_reject_bits; }
+
+/* Per-stream rejection report of the calling thread's next calls (orc_shard, orc_prepare_init,
+ * orc_helper_trace): rec is [ORC_REJ_STREAMS][ORC_REJ_REC] uint32, zeroed by the caller; stream
+ * row = {rejections, then up to ORC_REJ_MAX pairs (candidate position, element index)} for the
+ * streams 0 query rand, 1 measurement share, 2 proofs share, 3 joint rand, 4 prove rand.
+ * NULL turns it off. */
+#define ORC_REJ_STREAMS 5
+#define ORC_REJ_MAX 6
+#define ORC_REJ_REC (1 + 2 * ORC_REJ_MAX)
+static __thread uint32_t* t_rej_rec = NULL;
+static __thread int t_rej_stream = -1;
+void orc_reject_record(uint32_t* rec) { t_rej_rec = rec; }
+
 /* Xof.expand_into_vec with rejection sampling [VDAF-08 §6.2; prio Prng::get]. */
 static void xof_expand(const fld* F, xof_t* t, fe* out, uint32_t n) {
   int es = F->is128 ? 16 : 8;
+  const int rb = g_reject_bits;
   uint8_t buf[16];
-  for (uint32_t i = 0; i < n;) {
+  uint32_t cand = 0;
+  for (uint32_t i = 0; i < n; cand++) {
     xf_squeeze(t, buf, es);
     u128 v = 0;
     for (int k = es - 1; k >= 0; k--) v = (v << 8) | buf[k];
-    if (v < F->p) out[i++] = v;
+    const int top = rb && (uint32_t)(v >> (8 * es - rb)) == (1u << rb) - 1;
+    if (v < F->p && !top) {
+      out[i++] = v;
+    } else if (t_rej_rec && t_rej_stream >= 0) {
+      uint32_t* r = t_rej_rec + t_rej_stream * ORC_REJ_REC;
+      if (r[0] < ORC_REJ_MAX) {
+        r[1 + 2 * r[0]] = cand;
+        r[2 + 2 * r[0]] = i;
+      }
+      r[0]++;
+    }
   }
 }
 
@@ -886,7 +918,14 @@ static void expand_seed(const orc_params* p, const fld* F, const uint8_t* seed, 
   xof_for(p, &t, seed, usage);
   xf_absorb(&t, binder, blen);
   xf_finalize(&t);
+  t_rej_stream = usage == U_QUERY_RANDOMNESS   ? 0
+                 : usage == U_MEAS_SHARE       ? 1
+                 : usage == U_PROOF_SHARE      ? 2
+                 : usage == U_JOINT_RANDOMNESS ? 3
+                 : usage == U_PROVE_RANDOMNESS ? 4
+                                               : -1;
   xof_expand(F, &t, out, n);
+  t_rej_stream = -1;
   xf_free(&t);
 }
 static void derive_seed(const orc_params* p, const uint8_t* seed, uint16_t usage,

@@ -141,6 +141,17 @@ void orc_agg_merge(const orc_params* p, uint8_t* acc, const uint8_t* other);
 /* ns per Keccak-p[1600, 12] permutation and per Field128 multiply on one core */
 void orc_prim_bench(double* ns_perm, double* ns_mul);
 
+/* Test infrastructure (default off): bits = 1..24 makes every sampler also reject a candidate
+ * whose top `bits` bits are all ones, as the engine's test-rejection build does; 0 turns it off.
+ * Process-wide; set it while no batch call is running. */
+void orc_set_test_reject(int bits);
+int orc_get_test_reject(void);
+/* Rejection report of the calling thread's next orc_shard / orc_prepare_init / orc_helper_trace
+ * calls: rec is [5][13] uint32 zeroed by the caller, row s = {rejections, then up to 6 pairs
+ * (candidate position, element index)} of stream 0 query rand, 1 measurement share, 2 proofs
+ * share, 3 joint rand, 4 prove rand.  NULL turns it off. */
+void orc_reject_record(uint32_t* rec);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,16 @@ Field128 = Field(2**128 - 28 * 2**64 + 1, 16, 1450912666597565866187913296978976
 # ------------------------------------------------------------------------------------
 # XofTurboShake128
 # ------------------------------------------------------------------------------------
+# Test-rejection predicate (test infrastructure, default off): with reject_bits = b (1..24) the
+# samplers also reject a candidate whose top b bits, as a little-endian value, are all ones -- the
+# F::accept of the engine's test-rejection build and orc_set_test_reject of the C restatement.
+reject_bits = 0
+
+
+def accept(F: "Field", v: int, bits: int) -> bool:
+    return v < F.p and not (bits and (v >> (8 * F.es - bits)) == (1 << bits) - 1)
+
+
 class Xof:
     def __init__(self, seed: bytes, dst: bytes, binder: bytes):
         assert len(seed) == 16
@@ -173,11 +183,12 @@ class Xof:
     def next(self, n: int) -> bytes:
         return self.s.read(n)
 
-    def next_vec(self, F: Field, n: int) -> list[int]:
+    def next_vec(self, F: Field, n: int, bits: int | None = None) -> list[int]:
+        bits = reject_bits if bits is None else bits
         out = []
         while len(out) < n:
             v = int.from_bytes(self.next(F.es), "little")
-            if v < F.p:
+            if accept(F, v, bits):
                 out.append(v)
         return out
 
