@@ -2,36 +2,23 @@
 // shares [aggregation_job_writer.rs:591-695]; the launch functions are declared in prio3_host.h.
 //   run_accumulate     k_acc_seg + k_acc_fin / k_acc_fin_blk: masked, segmented mod-p reduction
 //   acc_multi_enqueue  k_acc_multi: the same for many small jobs of different runs in one launch
-//   fused_finish       k_zero, k_agg_waves, k_agg_fix, k_agg_final / _s: from the wave partials the
-//                      prepare kernels left (the fused accumulate's second half)
+//   fused_finish       k_agg_parts, k_agg_final / _s: from the wave partials the prepare kernels
+//                      left (the fused accumulate's second half)
 //   launch_combine, launch_batch_metadata, launch_combine_metadata   k_combine, k_meta*
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "prio3_host.h"
 #include "sha256_device.h"
 
-// Zero-fills up to 4 ranges in one launch (4-byte aligned lengths and pointers: 16-byte stores
-// for the aligned body, 4-byte stores at the ends)
-struct ZeroRanges {
-  uint8_t* dst[4];
-  size_t bytes[4];
-};
+// Zero-fills up to 4 ranges in one launch (zero_ranges, prio3_host.h): the first zeroing of a
+// fused run's accumulators where the run has no redo launch to do it (the leader's runs)
 __global__ __launch_bounds__(256) void k_zero(ZeroRanges z) {
-  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    uint8_t* d = z.dst[k];
-    const size_t n = z.bytes[k];
-    if (!d || !n) continue;
-    const size_t head = std::min(n, (size_t)((16 - ((uintptr_t)d & 15)) & 15));
-    const size_t n16 = (n - head) / 16;
-    for (size_t i = tid; i < n16; i += nth) ((uint4*)(d + head))[i] = make_uint4(0, 0, 0, 0);
-    for (size_t i = tid * 4; i < head; i += nth * 4) *(uint32_t*)(d + i) = 0u;
-    for (size_t i = head + 16 * n16 + tid * 4; i < n; i += nth * 4) *(uint32_t*)(d + i) = 0u;
-  }
+  zero_ranges(z, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 // ------------------------------------------------------------------------------------
@@ -39,7 +26,7 @@ __global__ __launch_bounds__(256) void k_zero(ZeroRanges z) {
 // ------------------------------------------------------------------------------------
 // Per-report inclusion: a report counts in its segment if its status is FINISHED, the host mask
 // is non-zero and its segment id is < n_segments.  A segment id past n_segments excludes the
-// report from every aggregate and count, on every path (fused: k_agg_fix; metadata: k_meta).
+// report from every aggregate and count, on every path (fused: k_agg_parts; metadata: k_meta).
 
 // Segmented partial sums in one pass over the output shares.  grid: x = output element, y =
 // report chunk, z = group of SG segments; each thread keeps SG running sums (one per segment of
@@ -222,18 +209,23 @@ __global__ __launch_bounds__(256) void k_acc_multi(const AccDesc* descs, uint8_t
 // Fused accumulate, second half: combine the per-wave half-limb partials per segment,
 // then fix up exclusions / non-fused reports and reduce mod p.
 // ------------------------------------------------------------------------------------
-// Level 1: grid (ceil(M*8/1024), chunks of WCH waves): thread = 4 consecutive slots (element,
+// k_agg_parts: one grid, two roles chosen by block index range.  The first fix_blocks blocks
+// take the fix role (agg_fix_role: status scan, counts, fix-up list), the others the waves role
+// (agg_waves_role: the wave partials).  The roles read disjoint inputs and write disjoint
+// outputs, so neither waits for the other, and the status scan runs under the partials read
+// where it was a launch of its own behind it; the fix blocks come first because each runs longer.
+// Waves role, blocks (bx < ceil(M*8/1024), chunk of WCH waves): thread = 4 consecutive slots (element,
 // half), read as one 16-byte load per wave (4x the bytes in flight of a slot per thread: the
 // 1-slot version moved the 134 MB of a 1 Mi batch's wave partials at 1.8 TB/s).  A chunk whose
 // fused waves all carry one segment writes 64-bit chunk partials (cseg[chunk] = its segment); a
 // chunk mixing segments adds each run with a 64-bit atomic into agg64 directly (cseg = ~0, as
 // for a chunk with no fused wave).
-__global__ __launch_bounds__(256) void k_agg_waves(uint32_t nwaves, uint32_t M,
-                                                   const uint32_t* wpart, const uint32_t* wseg,
-                                                   unsigned long long* cpart, uint32_t* cseg,
-                                                   unsigned long long* agg64) {
+__device__ __forceinline__ void agg_waves_role(uint32_t bx, uint32_t c, uint32_t nwaves,
+                                               uint32_t M, const uint32_t* wpart,
+                                               const uint32_t* wseg, unsigned long long* cpart,
+                                               uint32_t* cseg, unsigned long long* agg64) {
   static_assert(WCH <= 64, "one chunk's wave segments are read by one wave");
-  const uint32_t slot = 4 * (blockIdx.x * blockDim.x + threadIdx.x), c = blockIdx.y;
+  const uint32_t slot = 4 * (bx * blockDim.x + threadIdx.x);
   const uint32_t w0 = c * WCH, w1 = min(nwaves, w0 + WCH), lane = threadIdx.x & 63u;
   // the chunk's wave segments in one load per lane (not a dependent scalar load per wave):
   // bit i of `fused` = wave w0 + i was fused; s0 = the first fused wave's segment
@@ -241,7 +233,7 @@ __global__ __launch_bounds__(256) void k_agg_waves(uint32_t nwaves, uint32_t M,
   const uint64_t fused = __ballot(my != 0xffffffffu);
   const uint32_t s0 = fused ? (uint32_t)__shfl((int)my, __ffsll((long long)fused) - 1) : 0xffffffffu;
   const bool mixed = __any(my != 0xffffffffu && my != s0);
-  if (slot == 0 && blockIdx.x == 0) cseg[c] = mixed ? 0xffffffffu : s0;
+  if (slot == 0) cseg[c] = mixed ? 0xffffffffu : s0;
   if (s0 == 0xffffffffu) return;  // wave-uniform: no fused wave in the chunk
   // Lanes past the last slot (M * 8 is a multiple of 4, not of 256) stay alive through the mixed
   // path's readlane of `my` below: their loads are clamped to slot 0 and their atomics masked.
@@ -303,19 +295,33 @@ __global__ __launch_bounds__(256) void k_agg_waves(uint32_t nwaves, uint32_t M,
 // mask) per segment and lists every report whose fused inclusion differs (entry = r, or
 // r | 0x80000000 when it must be subtracted).  A block covers FIX_R consecutive reports and
 // keeps its counts in a small LDS table keyed by segment, flushed with one atomic per entry.
-// per: reports per block (4096 for large runs; 512 for the executor's 20-60k-report groups,
-// whose 4096-report blocks left most of the chip idle)
+// per: reports per block (1024 for large runs: a block's 4 trips end early enough to run under
+// the waves role's partials read, where the 16 trips of a 4096-report block outlasted it; 512
+// for the executor's 20-60k-report groups, whose larger blocks left most of the chip idle)
 constexpr uint32_t FIX_T = 64;
-static uint32_t fix_per(uint32_t n) { return n >= (1u << 18) ? 4096u : 512u; }
+static uint32_t fix_per(uint32_t n) { return n >= (1u << 18) ? 1024u : 512u; }
 // oor_masked: the fused kernel masked lanes with an out-of-range segment id out of its wave
 // partials (xofd_body); they are then not part of a fused wave's sum.  0: the wave partials
 // include them (the fused leader unpack), so they are subtracted like any excluded report.
-__global__ __launch_bounds__(256) void k_agg_fix(uint32_t n, const uint8_t* status,
-                                                 const uint32_t* seg, const uint8_t* accept,
-                                                 const uint32_t* wseg, uint32_t* fix,
-                                                 uint32_t fix_cap, uint32_t nseg,
-                                                 unsigned long long* counts, uint32_t oor_masked,
-                                                 uint32_t per, uint32_t wshift) {
+// fix: this finish's counter (Run::fix, one of the two); ents: the list; counts: Run::fcnt
+struct AggFixArgs {
+  uint32_t n;
+  const uint8_t* status;
+  const uint32_t* seg;
+  const uint8_t* accept;
+  uint32_t *fix, *ents;
+  uint32_t fix_cap, nseg;
+  unsigned long long* counts;
+  uint32_t oor_masked, per, wshift;
+};
+__device__ __forceinline__ void agg_fix_role(uint32_t blk, const AggFixArgs& a,
+                                             const uint32_t* wseg) {
+  const uint32_t n = a.n, nseg = a.nseg, wshift = a.wshift, oor_masked = a.oor_masked;
+  const uint32_t fix_cap = a.fix_cap, per = a.per;
+  const uint8_t *status = a.status, *accept = a.accept;
+  const uint32_t* seg = a.seg;
+  uint32_t *fix = a.fix, *ents = a.ents;
+  unsigned long long* counts = a.counts;
   __shared__ uint32_t tseg[FIX_T];
   __shared__ unsigned int tcnt[FIX_T];
   if (threadIdx.x < FIX_T) {
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(256) void k_agg_fix(uint32_t n, const uint8_t* stat
     tcnt[threadIdx.x] = 0;
   }
   __syncthreads();
-  const uint32_t lo = blockIdx.x * per, hi = min(n, lo + per);
+  const uint32_t lo = blk * per, hi = min(n, lo + per);
   for (uint32_t base = lo; base < hi; base += 256) {
     const uint32_t r = base + threadIdx.x;
     const bool valid = r < hi;
@@ -347,13 +353,27 @@ __global__ __launch_bounds__(256) void k_agg_fix(uint32_t n, const uint8_t* stat
       add(sg, 1u);
     }
     if (valid && fused != inc) {
-      const uint32_t i = atomicAdd(&fix[0], 1u);
-      if (i < fix_cap) fix[1 + i] = r | (inc ? 0u : 0x80000000u);
+      const uint32_t i = atomicAdd(fix, 1u);
+      if (i < fix_cap) ents[i] = r | (inc ? 0u : 0x80000000u);
     }
   }
   __syncthreads();
   if (threadIdx.x < FIX_T && tseg[threadIdx.x] != 0xffffffffu && tcnt[threadIdx.x])
     atomicAdd(&counts[tseg[threadIdx.x]], (unsigned long long)tcnt[threadIdx.x]);
+}
+
+// grid: fix_blocks + gx * nchunks blocks (see above)
+__global__ __launch_bounds__(256) void k_agg_parts(uint32_t fix_blocks, uint32_t gx, AggFixArgs fa,
+                                                   uint32_t nwaves, uint32_t M,
+                                                   const uint32_t* wpart, const uint32_t* wseg,
+                                                   unsigned long long* cpart, uint32_t* cseg,
+                                                   unsigned long long* agg64) {
+  if (blockIdx.x < fix_blocks) {  // block-uniform
+    agg_fix_role(blockIdx.x, fa, wseg);
+    return;
+  }
+  const uint32_t b = blockIdx.x - fix_blocks;
+  agg_waves_role(b % gx, b / gx, nwaves, M, wpart, wseg, cpart, cseg, agg64);
 }
 
 DEV f128 fold_halves_impl(const unsigned long long (&Hs)[8]);
@@ -363,11 +383,22 @@ DEV f128 fold_halves(const unsigned long long (&Hs)[8]) { return fold_halves_imp
 // partials of its segment for chunks cl, cl+32, ...; then the fix-up list is applied by all
 // 256 threads (lazily reduced signed sums), reduced through LDS, and thread 0 folds the
 // half-limb totals X = sum_h H_h 2^(16h) (H_h < 2^48) mod p.
+// The final kernels leave the run's accumulators clean for its next finish (no zeroing launch):
+// each block zeroes the agg64 words it has read, the element-0 block of a segment moves the
+// segment's count from the count row to counts[s] and zeroes it, and the first block zeroes the
+// other generation's fix-up counter (fa.next), which no block of this finish reads.
+struct AggFinalArgs {
+  const uint32_t* nfix;  // this finish's fix-up counter
+  const uint32_t* ents;  // the list
+  uint32_t* next;        // the next finish's counter
+  unsigned long long* fcnt;
+  unsigned long long* counts;
+};
 __global__ __launch_bounds__(256) void k_agg_final(uint32_t M, size_t ld,
-                                                   const unsigned long long* agg64,
+                                                   unsigned long long* agg64,
                                                    uint32_t nchunks,
                                                    const unsigned long long* cpart,
-                                                   const uint32_t* cseg, const uint32_t* fix,
+                                                   const uint32_t* cseg, AggFinalArgs fa,
                                                    const uint32_t* seg, const void* meas,
                                                    uint8_t* agg) {
   const uint32_t idx = blockIdx.x, s = idx / M, e = idx % M;
@@ -380,9 +411,9 @@ __global__ __launch_bounds__(256) void k_agg_final(uint32_t M, size_t ld,
   red[tid] = acc;
   // fix-up entries, strided over the block
   f128 ad = zero128(), sb = zero128();
-  const uint32_t nfix = fix[0];
+  const uint32_t nfix = *fa.nfix;
   for (uint32_t i = tid; i < nfix; i += 256) {
-    const uint32_t ent = fix[1 + i], r = ent & 0x7fffffffu;
+    const uint32_t ent = fa.ents[i], r = ent & 0x7fffffffu;
     if ((seg ? seg[r] : 0u) != s) continue;
     const f128 x = Fp128::load(meas, (size_t)e * ld + r);
     if (ent & 0x80000000u) sb = add128(sb, x);
@@ -395,7 +426,8 @@ __global__ __launch_bounds__(256) void k_agg_final(uint32_t M, size_t ld,
     if (tid < st) red[tid] += red[tid + st];
     __syncthreads();
   }
-  for (uint32_t st = 128; st >= 1; st >>= 1) {
+  // (an empty list, block-uniform: fadd[0] and fsub[0] are zero as they stand)
+  for (uint32_t st = nfix ? 128 : 0; st >= 1; st >>= 1) {
     if (tid < st) {
       fadd[tid] = add128(fadd[tid], fadd[tid + st]);
       fsub[tid] = add128(fsub[tid], fsub[tid + st]);
@@ -404,7 +436,15 @@ __global__ __launch_bounds__(256) void k_agg_final(uint32_t M, size_t ld,
   }
   if (tid != 0) return;
   unsigned long long Hs[8];
-  for (int hh = 0; hh < 8; hh++) Hs[hh] = red[hh] + agg64[(size_t)idx * 8 + hh];
+  for (int hh = 0; hh < 8; hh++) {
+    Hs[hh] = red[hh] + agg64[(size_t)idx * 8 + hh];
+    agg64[(size_t)idx * 8 + hh] = 0;
+  }
+  if (e == 0) {
+    fa.counts[s] = fa.fcnt[s];
+    fa.fcnt[s] = 0;
+  }
+  if (idx == 0) *fa.next = 0;
   Fp128::store(agg, idx, sub128(add128(fold_halves(Hs), fadd[0]), fsub[0]));
 }
 
@@ -413,23 +453,32 @@ __global__ __launch_bounds__(256) void k_agg_final(uint32_t M, size_t ld,
 // block does not reduce 256 threads through LDS for one element; the fix-up list (empty when
 // every wave fused) is split over the 8 halves and summed by shuffles.
 __global__ __launch_bounds__(256) void k_agg_final_s(uint32_t M, size_t ld,
-                                                     const unsigned long long* agg64,
+                                                     unsigned long long* agg64,
                                                      uint32_t nchunks,
                                                      const unsigned long long* cpart,
-                                                     const uint32_t* cseg, const uint32_t* fix,
+                                                     const uint32_t* cseg, AggFinalArgs fa,
                                                      const uint32_t* seg, const void* meas,
                                                      uint8_t* agg) {
   const uint32_t s = blockIdx.y, tid = threadIdx.x, h = tid & 7u, lane = tid & 63u;
   const uint32_t e = blockIdx.x * 32u + (tid >> 3);
   const bool live = e < M;
   const uint32_t ec = live ? e : 0u;
-  unsigned long long H = agg64[((size_t)s * M + ec) * 8 + h];
+  unsigned long long H = 0;
+  if (live) {  // (a dead thread's H is not used)
+    H = agg64[((size_t)s * M + e) * 8 + h];
+    agg64[((size_t)s * M + e) * 8 + h] = 0;
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    fa.counts[s] = fa.fcnt[s];
+    fa.fcnt[s] = 0;
+    if (s == 0) *fa.next = 0;
+  }
   for (uint32_t c = 0; c < nchunks; c++)
     if (cseg[c] == s) H += cpart[((size_t)c * M + ec) * 8 + h];
   f128 ad = zero128(), sb = zero128();
-  const uint32_t nfix = fix[0];
+  const uint32_t nfix = *fa.nfix;
   for (uint32_t i = h; i < nfix; i += 8) {
-    const uint32_t ent = fix[1 + i], r = ent & 0x7fffffffu;
+    const uint32_t ent = fa.ents[i], r = ent & 0x7fffffffu;
     if ((seg ? seg[r] : 0u) != s) continue;
     const f128 x = Fp128::load(meas, (size_t)ec * ld + r);
     if (ent & 0x80000000u) sb = add128(sb, x);
@@ -547,10 +596,11 @@ __global__ void k_meta_init(uint32_t n_segments, uint32_t* ck, unsigned long lon
 // batch of one segment issues ~5 k atomics on the segment's 10 words instead of ~41 k from
 // 256-report blocks, whose serialisation on those addresses had set the kernel's time (112 us).
 constexpr uint32_t META_T = 1024, META_W = META_T / 64, META_BLOCKS = 512;
-__global__ __launch_bounds__(1024) void k_meta(uint32_t n, const uint8_t* ids, const uint64_t* times,
-                                             const uint8_t* status, const uint8_t* mask,
-                                             const uint32_t* seg, uint32_t n_segments, uint32_t* ck,
-                                             unsigned long long* iv) {
+__global__ __launch_bounds__(1024) void k_meta_seg(uint32_t n, const uint8_t* ids,
+                                                 const uint64_t* times,
+                                                 const uint8_t* status, const uint8_t* mask,
+                                                 const uint32_t* seg, uint32_t n_segments,
+                                                 uint32_t* ck, unsigned long long* iv) {
   __shared__ uint32_t s_seg0;
   __shared__ uint32_t s_ck[META_W][8];
   __shared__ unsigned long long s_lo[META_W], s_hi[META_W];
@@ -634,6 +684,172 @@ __global__ __launch_bounds__(1024) void k_meta(uint32_t n, const uint8_t* ids, c
     __syncthreads();  // s_seg0 / s_ck of this tile are read before the next tile writes them
   }
   flush();
+}
+
+// k_meta: the whole job in one launch, for up to META_FAST_SEGS segments (a batch, or a job's
+// few batch buckets).  A block keeps (XOR, min, max) per segment in LDS over its tiles -- a
+// uniform tile folded in by threads 0..8, a tile that mixes segments by LDS atomics -- and writes
+// them unconditionally to its row of `rows`, so nothing needs initialising and no global atomic
+// runs on the segment's words.  The block that draws the last ticket (one atomic increment
+// behind the drained row stores; no block waits for another) reduces the rows, writes the checksums and the finished
+// (start, duration) pairs -- (0, 0) for a segment with no report -- and puts the ticket back
+// to zero for the next call on its stream.
+constexpr uint32_t META_FAST_SEGS = 8;
+struct MetaRow {
+  uint32_t ck[8];
+  unsigned long long lo, hi;
+};
+constexpr uint32_t META_COLS = 10;  // a row's values per segment: 8 checksum words, lo, hi
+__global__ __launch_bounds__(1024) void k_meta(uint32_t n, const uint8_t* ids,
+                                             const uint64_t* times, const uint8_t* status,
+                                             const uint8_t* mask, const uint32_t* seg,
+                                             uint32_t n_segments, uint32_t* ck,
+                                             unsigned long long* iv, MetaRow* rows,
+                                             uint32_t* ticket) {
+  __shared__ uint32_t s_seg0;
+  __shared__ uint32_t s_ck[META_W][8];
+  __shared__ unsigned long long s_lo[META_W], s_hi[META_W];
+  __shared__ uint32_t t_ck[META_FAST_SEGS][8];
+  __shared__ unsigned long long t_lo[META_FAST_SEGS], t_hi[META_FAST_SEGS];
+  __shared__ unsigned long long s_red[META_T];  // [group][column], the last block's fold
+  __shared__ unsigned long long s_fin[8][META_FAST_SEGS * META_COLS];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  if (tid < META_FAST_SEGS * 8) t_ck[tid >> 3][tid & 7u] = 0;
+  if (tid < META_FAST_SEGS) {
+    t_lo[tid] = ~0ull;
+    t_hi[tid] = 0;
+  }
+  __syncthreads();
+  for (uint32_t base = blockIdx.x * META_T; base < n; base += gridDim.x * META_T) {
+    const uint32_t r = base + tid;
+    const bool valid = r < n;
+    const uint32_t sg = valid ? (seg ? seg[r] : 0u) : 0xffffffffu;
+    const bool in_range = valid && sg < n_segments;
+    const bool inc = in_range && status[r] == PRIO3_STATUS_FINISHED && (!mask || mask[r]);
+    uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ck && inc) {
+      uint32_t id[4];
+      load16(ids + 16 * (size_t)r, id);
+      sha256_id16(id, h);
+    }
+    unsigned long long lo = ~0ull, hi = 0;
+    if (times && in_range) {
+      lo = times[r];
+      hi = lo + 1;  // Interval::from_time: [t, t + 1)
+    }
+    if (tid == 0) s_seg0 = sg;  // thread 0 of a tile is always a valid report
+    __syncthreads();
+    const bool uniform = __syncthreads_and(!valid || sg == s_seg0) && s_seg0 < n_segments;
+    if (uniform) {
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) h[i] ^= (uint32_t)__shfl_xor((int)h[i], off);
+        const unsigned long long l2 = __shfl_xor(lo, off), h2 = __shfl_xor(hi, off);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) s_ck[wv][i] = h[i];
+        s_lo[wv] = lo;
+        s_hi[wv] = hi;
+      }
+      __syncthreads();
+      if (tid < 8) {
+        uint32_t x = 0;
+        for (uint32_t q = 0; q < META_W; q++) x ^= s_ck[q][tid];
+        t_ck[s_seg0][tid] ^= x;
+      }
+      if (tid == 8) {
+        unsigned long long a = t_lo[s_seg0], b = t_hi[s_seg0];
+        for (uint32_t q = 0; q < META_W; q++) {
+          a = s_lo[q] < a ? s_lo[q] : a;
+          b = s_hi[q] > b ? s_hi[q] : b;
+        }
+        t_lo[s_seg0] = a;
+        t_hi[s_seg0] = b;
+      }
+    } else {
+      if (ck && inc)
+#pragma unroll
+        for (int i = 0; i < 8; i++) atomicXor(&t_ck[sg][i], h[i]);
+      if (times && in_range) {
+        atomicMin(&t_lo[sg], lo);
+        atomicMax(&t_hi[sg], hi);
+      }
+    }
+    __syncthreads();  // s_seg0 / s_ck / the table of this tile are done before the next tile
+  }
+  // the block's row, every word of it
+  const uint32_t ncols = n_segments * META_COLS;
+  MetaRow* my = rows + (size_t)blockIdx.x * n_segments;
+  // (write-through stores, drained by every wave ahead of the barrier: the block needs no
+  // release fence, which would write back all of its die's L2)
+  if (tid < n_segments * 8)
+    __hip_atomic_store(&my[tid >> 3].ck[tid & 7u], t_ck[tid >> 3][tid & 7u], __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  if (tid >= 64 && tid < 64 + n_segments) {
+    __hip_atomic_store(&my[tid - 64].lo, t_lo[tid - 64], __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&my[tid - 64].hi, t_hi[tid - 64], __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t t =
+        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = t == gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    s_seg0 = last ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_seg0) return;  // block-uniform
+  // the last block: thread (column c = tid % ncols, group g = tid / ncols) folds rows g, g + G,
+  // ... -- every thread with a few independent loads, not a few threads with many in a row (the
+  // rows come from the other dies' L2 at ~1 us a load) -- then the G partials through LDS in
+  // two steps
+  const uint32_t G = META_T / ncols, c = tid % ncols, g = tid / ncols;
+  auto fold = [](uint32_t k, unsigned long long v, unsigned long long x) {
+    return k < 8 ? v ^ x : k == 8 ? (x < v ? x : v) : (x > v ? x : v);
+  };
+  if (g < G) {
+    const uint32_t s = c / META_COLS, k = c % META_COLS;
+    unsigned long long v = k == 8 ? ~0ull : 0ull;
+    for (uint32_t b = g; b < gridDim.x; b += G) {
+      const MetaRow* row = rows + (size_t)b * n_segments + s;
+      v = fold(k, v, k < 8 ? row->ck[k] : k == 8 ? row->lo : row->hi);
+    }
+    s_red[g * ncols + c] = v;
+  }
+  __syncthreads();
+  if (tid < 8 * ncols) {  // part q = tid / ncols of 8: groups q, q + 8, ...
+    const uint32_t k = c % META_COLS;
+    unsigned long long v = k == 8 ? ~0ull : 0ull;
+    for (uint32_t q = g; q < G; q += 8) v = fold(k, v, s_red[q * ncols + c]);
+    s_fin[g][c] = v;
+  }
+  __syncthreads();
+  if (tid < ncols) {
+    const uint32_t k = c % META_COLS;
+    unsigned long long v = s_fin[0][c];
+    for (uint32_t q = 1; q < 8; q++) v = fold(k, v, s_fin[q][c]);
+    s_fin[0][c] = v;  // (only this thread reads or writes column c of part 0 here)
+  }
+  __syncthreads();
+  if (tid < n_segments * 8 && ck)
+    ck[tid] = (uint32_t)s_fin[0][(tid >> 3) * META_COLS + (tid & 7u)];
+  if (tid >= 64 && tid < 64 + n_segments && iv) {
+    const uint32_t s = tid - 64;
+    const unsigned long long lo = s_fin[0][s * META_COLS + 8], hi = s_fin[0][s * META_COLS + 9];
+    iv[2 * s] = hi ? lo : 0;
+    iv[2 * s + 1] = hi ? hi - lo : 0;
+  }
+  if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // multi-GPU combine of k per-rank metadata: checksums XOR, intervals Interval::merge
@@ -733,7 +949,19 @@ int run_accumulate(prio3_engine* e, Run* R, uint32_t c0, uint32_t n, const uint8
   return rc;
 }
 
-// k_agg_waves (chunk partials), k_agg_fix (counts and the reports whose fused inclusion differs
+ZeroRanges fused_first_zero(const Run* R) {
+  ZeroRanges z{};
+  const size_t S = R->nseg ? R->nseg : 1;
+  z.dst[0] = (uint8_t*)R->agg64;
+  z.bytes[0] = S * R->dp.meas_len * 8 * 8;
+  z.dst[1] = (uint8_t*)R->fix;
+  z.bytes[1] = 2 * sizeof(uint32_t);
+  z.dst[2] = (uint8_t*)R->fcnt;
+  z.bytes[2] = 8 * S;
+  return z;
+}
+
+// k_agg_parts (chunk partials beside the counts and the reports whose fused inclusion differs
 // from their verdict), k_agg_final.  seg: the inclusion segment ids; fix_seg: the segment each
 // fix-up entry applies to (nullptr: 0 -- the leader's partials are all summed for segment 0, so
 // with one segment every fix-up, an out-of-range id included, is a correction of segment 0).
@@ -742,34 +970,37 @@ int fused_finish(prio3_engine* e, Run* R, const uint8_t* d_status, const uint32_
                  uint8_t* d_agg_shares, uint64_t* d_counts, hipStream_t st) {
   const uint32_t n = R->n, M = R->dp.meas_len, ws = R->wshift;
   const uint32_t nwaves = (n + (1u << ws) - 1) >> ws;
-  {  // one zeroing launch for the three accumulators (three memsets were ~15 us per group, r03ag)
-    ZeroRanges z{};
-    z.dst[0] = (uint8_t*)R->agg64;
-    z.bytes[0] = (size_t)S * M * 8 * 8;
-    z.dst[1] = (uint8_t*)R->fix;
-    z.bytes[1] = sizeof(uint32_t);
-    z.dst[2] = (uint8_t*)d_counts;
-    z.bytes[2] = 8 * (size_t)S;
+  // The accumulators are clean after the run's redo launch and after every finish (the final
+  // kernels zero what they consume); only a run without a redo launch, or one whose last finish
+  // failed half way, needs the zeroing launch.
+  if (!R->fclean) {
+    const ZeroRanges z = fused_first_zero(R);
     TIMED(e, st, "k_zero", (k_zero<<<std::min<uint32_t>(256, (uint32_t)((z.bytes[0] / 16 + 255) / 256) + 1), 256, 0, st>>>(z)));
+    R->fgen = 0;
   }
+  R->fclean = false;
+  const uint32_t g = R->fgen & 1u;
   const uint32_t nchunks = (nwaves + WCH - 1) / WCH;
-  dim3 g1((M * 8 / 4 + 255) / 256, nchunks);  // 4 slots per thread (k_agg_waves)
-  TIMED(e, st, "k_agg_waves",
-        (k_agg_waves<<<g1, 256, 0, st>>>(nwaves, M, R->wpart, R->wseg, R->cpart, R->cseg,
-                                         R->agg64)));
-  TIMED(e, st, "k_agg_fix",
-        (k_agg_fix<<<(n + fix_per(n) - 1) / fix_per(n), 256, 0, st>>>(
-            n, d_status, seg, d_accept_mask, R->wseg, R->fix, (uint32_t)(R->fix_cap - 1), S,
-            (unsigned long long*)d_counts, fix_seg ? 1u : 0u, fix_per(n), ws)));
+  const uint32_t gx = (M * 8 / 4 + 255) / 256;  // 4 slots per thread (the waves role)
+  const uint32_t fix_blocks = (n + fix_per(n) - 1) / fix_per(n);
+  AggFixArgs fx{n, d_status, seg, d_accept_mask, R->fix + g, R->fix + 2, (uint32_t)R->fix_cap, S,
+                R->fcnt, fix_seg ? 1u : 0u, fix_per(n), ws};
+  TIMED(e, st, "k_agg_parts",
+        (k_agg_parts<<<fix_blocks + gx * nchunks, 256, 0, st>>>(
+            fix_blocks, gx, fx, nwaves, M, R->wpart, R->wseg, R->cpart, R->cseg, R->agg64)));
+  const AggFinalArgs fa{R->fix + g, R->fix + 2, R->fix + (g ^ 1u), R->fcnt,
+                        (unsigned long long*)d_counts};
   if (nchunks <= 64 && S > 1)
     TIMED(e, st, "k_agg_final",
           (k_agg_final_s<<<dim3((M + 31) / 32, S), 256, 0, st>>>(
-              M, R->dp.ld, R->agg64, nchunks, R->cpart, R->cseg, R->fix, fix_seg, R->sc.meas,
+              M, R->dp.ld, R->agg64, nchunks, R->cpart, R->cseg, fa, fix_seg, R->sc.meas,
               d_agg_shares)));
   else
     TIMED(e, st, "k_agg_final",
           (k_agg_final<<<S * M, 256, 0, st>>>(M, R->dp.ld, R->agg64, nchunks, R->cpart, R->cseg,
-                                               R->fix, fix_seg, R->sc.meas, d_agg_shares)));
+                                               fa, fix_seg, R->sc.meas, d_agg_shares)));
+  R->fgen++;
+  R->fclean = true;
   return PRIO3_OK;
 }
 
@@ -820,16 +1051,64 @@ int launch_combine(prio3_engine* e, uint32_t k, uint32_t n_segments, const uint8
   });
 }
 
+// The area of stream_zero_words (prio3_host.h): launch_batch_metadata takes no engine lock, so
+// calls on two streams may run at once and must not share a ticket.  The area (256 bytes of
+// counters, then META_BLOCKS x META_FAST_SEGS rows: 193 KiB) is allocated at a stream's first
+// call and its counters zeroed once on that stream ahead of the launch; the calls after the
+// first add neither a memset nor an event.  The areas live as long as the process.
+constexpr size_t STREAM_ZERO_MAX = 64;
+uint32_t* stream_zero_words(int device, hipStream_t st, std::mutex** smu) {
+  struct Ctx {
+    int device;
+    hipStream_t st;
+    uint32_t* mem;
+    std::mutex* mu;
+  };
+  static std::mutex mu;
+  static std::vector<Ctx> all;
+  std::lock_guard<std::mutex> lk(mu);
+  for (const Ctx& c : all)
+    if (c.device == device && c.st == st) {
+      if (smu) *smu = c.mu;
+      return c.mem;
+    }
+  if (all.size() >= STREAM_ZERO_MAX) return nullptr;
+  uint32_t* mem = nullptr;
+  const size_t bytes = 256 + sizeof(MetaRow) * META_BLOCKS * META_FAST_SEGS;
+  if (hipMalloc((void**)&mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  if (hipMemsetAsync(mem, 0, 256, st) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(mem);
+    return nullptr;
+  }
+  all.push_back(Ctx{device, st, mem, new std::mutex});
+  if (smu) *smu = all.back().mu;
+  return mem;
+}
+
 int launch_batch_metadata(prio3_engine* e, uint32_t n, const uint8_t* d_report_ids,
                           const uint64_t* d_times, const uint8_t* d_status,
                           const uint8_t* d_accept_mask, const uint32_t* d_segment_ids,
                           uint32_t n_segments, uint32_t* ck, unsigned long long* iv,
                           hipStream_t st) {
+  if (n_segments <= META_FAST_SEGS)
+    if (uint32_t* ctx = stream_zero_words(e->device, st)) {
+      const uint32_t blocks = std::max(1u, std::min((n + META_T - 1) / META_T, META_BLOCKS));
+      TIMED(e, st, "k_meta",
+            (k_meta<<<blocks, META_T, 0, st>>>(n, d_report_ids, d_times, d_status, d_accept_mask,
+                                               d_segment_ids, n_segments, ck, iv,
+                                               (MetaRow*)(ctx + 64), ctx)));
+      return PRIO3_OK;
+    }
+  // many segments (or no ticket left): init, per-segment atomics, final
   const uint32_t sb = (n_segments + 255) / 256;
   TIMED(e, st, "k_meta_init", (k_meta_init<<<sb, 256, 0, st>>>(n_segments, ck, iv)));
   if (n)
     TIMED(e, st, "k_meta",
-          (k_meta<<<std::min((n + META_T - 1) / META_T, META_BLOCKS), META_T, 0, st>>>(
+          (k_meta_seg<<<std::min((n + META_T - 1) / META_T, META_BLOCKS), META_T, 0, st>>>(
               n, d_report_ids, d_times, d_status, d_accept_mask, d_segment_ids, n_segments, ck,
               d_times ? iv : nullptr)));
   if (iv) TIMED(e, st, "k_meta_final", (k_meta_final<<<sb, 256, 0, st>>>(n_segments, iv)));

@@ -138,6 +138,12 @@ struct Scratch {
   const uint32_t* seg;
   uint32_t* wpart;
   uint32_t* wseg;
+  // k_prep_h's redo list (nullable: the redo launch scans the flags): redo_cnt[0] the number of
+  // flagged reports, redo_cnt[1] the redo launch's ticket -- both zero whenever a prepare starts
+  // (stream_zero_words) -- and redo_list[i] = redo_c0 + r, the run's column of the i-th of them
+  uint32_t* redo_cnt = nullptr;
+  uint32_t* redo_list = nullptr;
+  uint32_t redo_c0 = 0;
 };
 
 struct OutPtrs {
@@ -640,9 +646,18 @@ struct Run {
           *linput = nullptr, *msgs = nullptr, *status = nullptr;
   // fused accumulate (prio3_device_prepare_aggregate)
   uint32_t *wpart = nullptr, *wseg = nullptr, *cseg = nullptr, *fix = nullptr;
+  uint32_t* redo_list = nullptr;  // k_prep_h's flagged reports (Scratch::redo_list), n entries
   uint4* corr_all = nullptr;  // FPVec: corrected joint-rand seeds of all n reports (leader)
   unsigned long long *cpart = nullptr, *agg64 = nullptr;
   size_t fix_cap = 0;
+  // fix[0], fix[1]: the fix-up list's length of the even / odd fused_finish of the run (the
+  // finish of generation g zeroes the counter of g + 1); the entries follow at fix[2].
+  // fcnt: the per-segment counts of the finish under way.  fclean: agg64, fix[0..1] and fcnt are
+  // zero -- after the run's redo launch or a k_zero, and again after every finish, whose last
+  // kernel zeroes what it has consumed.
+  unsigned long long* fcnt = nullptr;
+  uint32_t fgen = 0;
+  bool fclean = false;
   bool fused = false;
   bool aggregate = false;  // made by prio3_device_prepare_aggregate (finish may follow)
   bool lfused = false;     // leader init summed the wave partials (segment 0; leader_fuse_acc)

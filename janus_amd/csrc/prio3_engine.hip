@@ -466,6 +466,7 @@ static size_t run_carve(Run* R, unsigned flags, uint8_t* base) {
     take(&R->sc.acc, fp ? 16 : es * d.arity * ld);
     take(&R->sc.out, own_out(d) ? es * d.out_len * ldo : 16);
     take(&R->sc.beta, es * d.calls * ld);
+    if (es == 16 && d.P == 32) take(&R->redo_list, 4 * n);  // (the k_prep_h instances)
     // FPVec runs in sub-batches of ld columns: the leader's corrected seeds of every report
     // outlive their sub-batch's scratch (prepare_next reads them)
     if (fp) take(&R->corr_all, 16 * n);
@@ -505,7 +506,8 @@ static size_t run_carve(Run* R, unsigned flags, uint8_t* base) {
     take(&R->cpart, chunks * M * 8 * 8);
     take(&R->cseg, chunks * sizeof(uint32_t));
     take(&R->agg64, (size_t)(R->nseg ? R->nseg : 1) * M * 8 * 8);
-    take(&R->fix, (n + 1) * sizeof(uint32_t));
+    take(&R->fix, (n + 2) * sizeof(uint32_t));
+    take(&R->fcnt, 8 * (size_t)(R->nseg ? R->nseg : 1));
   }
   return off;
 }
@@ -538,7 +540,7 @@ static Run* run_create(prio3_engine* e, uint32_t n, unsigned flags, uint32_t nse
   }
   run_carve(R, flags, R->slab->base);
   R->keep = e->keep_scratch != 0;
-  R->fix_cap = (size_t)n + 1;
+  R->fix_cap = (size_t)n;  // entries behind the two counters
   R->last = st;
   return R;
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <mutex>
 #include <vector>
 
 #include "prio3_common.h"
@@ -75,7 +76,43 @@ static inline const uint8_t* run_out_shares(const Run* R, uint32_t c0) {
   return (const uint8_t*)(own_out(R->dp) ? R->sc.out : R->sc.meas) + (size_t)R->dp.es * c0;
 }
 
-constexpr uint32_t WCH = 32;  // waves per fused-partial chunk (k_agg_waves, run_carve)
+constexpr uint32_t WCH = 32;  // waves per fused-partial chunk (k_agg_parts, run_carve)
+
+// Zero-fill of up to 4 ranges by the threads of a launch (4-byte aligned lengths and pointers:
+// 16-byte stores for the aligned body, 4-byte stores at the ends).  k_zero is that launch; a
+// fused run's k_slow_redo* launch takes the ranges along instead (fused_first_zero), so the run's
+// accumulators are clean before its first fused_finish without a launch of their own.
+struct ZeroRanges {
+  uint8_t* dst[4];
+  size_t bytes[4];
+};
+__device__ __forceinline__ void zero_ranges(const ZeroRanges& z, size_t tid, size_t nth) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint8_t* d = z.dst[k];
+    const size_t n = z.bytes[k];
+    if (!d || !n) continue;
+    const size_t h0 = (16 - ((uintptr_t)d & 15)) & 15, head = n < h0 ? n : h0;
+    const size_t n16 = (n - head) / 16;
+    for (size_t i = tid; i < n16; i += nth) ((uint4*)(d + head))[i] = make_uint4(0, 0, 0, 0);
+    for (size_t i = tid * 4; i < head; i += nth * 4) *(uint32_t*)(d + i) = 0u;
+    for (size_t i = head + 16 * n16 + tid * 4; i < n; i += nth * 4) *(uint32_t*)(d + i) = 0u;
+  }
+}
+// The accumulators fused_finish adds into and leaves clean again: the 64-bit sums of the mixed
+// chunks, the two fix-up counters and the count row.  (Defined in prio3_accumulate.hip.)
+ZeroRanges fused_first_zero(const Run* R);
+// 64 words of device memory per (GPU, stream), zero at the stream's first call and put back to
+// zero by the last block of every launch that counts in them -- [0] k_meta's ticket, [1] the
+// redo list's length and [2] the list launch's ticket (Scratch::redo_cnt = words + 1) -- so the
+// steady path needs no memset.  Calls on one stream follow each other and share the words;
+// calls on two streams, which may run at once, do not.  k_meta's rows follow at byte 256.
+// nullptr past STREAM_ZERO_MAX streams: the caller then takes its path without them.
+// *mu (optional): the stream's mutex, for a caller that counts in the words over several launches
+// (prepare_run: from k_prep_h's appends to the redo launch) and so must keep another thread's
+// launches on the same stream from falling between them.
+// (Defined in prio3_accumulate.hip.)
+uint32_t* stream_zero_words(int device, hipStream_t st, std::mutex** mu = nullptr);
 
 // a pooled stream for one blocking host-buffer call
 struct PooledStream {

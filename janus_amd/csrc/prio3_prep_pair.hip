@@ -20,7 +20,7 @@
 //          beta_k and the 16 wires are split between the two lanes (same instruction stream,
 //          lane-dependent data); the partial G, S, sum_L, p(t) and range meet by one DPP swap
 // A wave holds 32 reports: wave partials and wave segments are indexed by r >> 5
-// (DevParams-independent; fused_finish passes wshift = 5 to k_agg_fix for these runs).
+// (DevParams-independent; fused_finish passes wshift = 5 to k_agg_parts for these runs).
 // Flagged reports (rejection sampling) are deferred to the run's k_slow_redo, as k_prep_h's.
 #include <hip/hip_runtime.h>
 

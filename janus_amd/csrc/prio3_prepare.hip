@@ -217,7 +217,10 @@ __global__ __launch_bounds__(256, XOFD_OCC) void k_xof(DevParams p, InPtrs in, S
 // (in.leader_src) into in.leader in 16-byte pieces spread over the share loop -- each load issued
 // before the iteration's two permutations and stored after them, so the PCIe latency hides under
 // the Keccak work and the transfer runs at the XOF's pace -- plus its segment id and accept byte.
-template <bool FUSE, bool TR = false, bool PULL = false>
+// LIST (k_prep_h): flagged lanes append their report to the run's redo list (Scratch::redo_cnt,
+// redo_list) -- under a wave-uniform test of the ballot, one atomic per wave on the counter -- so
+// the run's redo launch strides over the list instead of scanning every flag byte.
+template <bool FUSE, bool TR = false, bool PULL = false, bool LIST = false>
 __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, const Scratch& sc,
                                           const uint32_t r) {  // r & 63 == this lane
   typedef Fp128 F;
@@ -229,7 +232,7 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
     const uint32_t sg = valid ? (sc.seg ? sc.seg[r] : 0u) : 0xffffffffu;
     // A segment id >= n_segments puts the report in no aggregate.  Such lanes (the executor's
     // pad columns between jobs, excluded reports) are masked out of the wave partials, so they
-    // do not keep the wave's other 63 reports from fusing; k_agg_fix knows them (oor_masked).
+    // do not keep the wave's other 63 reports from fusing; k_agg_parts knows them (oor_masked).
     const uint64_t inr = __ballot(valid && sg < p.nseg);
     s0 = inr ? (uint32_t)__shfl((int)sg, __ffsll((long long)inr) - 1) : 0xffffffffu;
     oor = valid && sg >= p.nseg;
@@ -505,6 +508,17 @@ __device__ __forceinline__ void xofd_body(const DevParams& p, const InPtrs& in, 
     sc.corrected[r] = make_uint4(cor[0], cor[1], cor[2], cor[3]);
   }
   sc.flag[r] = (uint8_t)flag;
+  if constexpr (LIST) {
+    const uint64_t fm = __ballot(flag != 0);
+    if (fm && sc.redo_cnt) {  // wave-uniform
+      const uint32_t first = (uint32_t)__ffsll((long long)fm) - 1u;
+      uint32_t base = 0;
+      if (lane == first) base = atomicAdd(sc.redo_cnt, (uint32_t)__popcll(fm));
+      base = (uint32_t)__shfl((int)base, (int)first);
+      if (flag)
+        sc.redo_list[base + (uint32_t)__popcll(fm & ((1ull << lane) - 1ull))] = sc.redo_c0 + r;
+    }
+  }
   if constexpr (FUSE) {
     if (fuse) {  // all 64 lanes are live here
       const bool anyflag = __any(flag != 0);
@@ -755,7 +769,7 @@ __global__ __launch_bounds__(256, JR_OCC) void k_jrpart(DevParams p, InPtrs in, 
 // ------------------------------------------------------------------------------------
 // wpart / wseg (non-null: the device leader's fused accumulate, leader_fuse_acc): while a chunk
 // sits in LDS, thread (element tid / 8, half-limb tid % 8) also sums that 16-bit half-limb over
-// the block's 64 reports -- the wave partials k_agg_waves reads (the layout of wave_halfsum2's)
+// the block's 64 reports -- the wave partials k_agg_parts reads (the layout of wave_halfsum2's)
 // -- and the block's wave is marked fused for segment 0 when all 64 reports are present and
 // canonical.
 __global__ __launch_bounds__(256) void k_leader_unpack(DevParams p, InPtrs in, Scratch sc,
@@ -1918,7 +1932,7 @@ template <bool FUSE, bool PULL = false>
 __global__ __launch_bounds__(XOFD_BLOCK, 3) void k_prep_h(DevParams p, InPtrs in, Scratch sc,
                                                    OutPtrs out) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  xofd_body<FUSE, false, PULL>(p, in, sc, r);
+  xofd_body<FUSE, false, PULL, true>(p, in, sc, r);
   // two wires per sweep: 3 and 4 spill inside the wire loop
   query_h_body<2, 32>(p, in, sc, out, r);
 }
@@ -1955,8 +1969,34 @@ __global__ __launch_bounds__(256, 3) void k_prep_sum(DevParams p, InPtrs in, Scr
 // k_slow_redo<PP>: both halves in one launch -- each lane scans the flags of REDO_RPL reports
 // (16-byte loads) and, for a flagged report, re-runs its XOF (flag := 2) and then its query on
 // the same lane.
+// z: the accumulators of a fused run's aggregate (fused_first_zero), zeroed here by the launch's
+// threads ahead of their scan, so that the run's first fused_finish needs no zeroing launch;
+// empty for the other runs.
 template <int PP>
-__global__ __launch_bounds__(64) void k_slow_redo(DevParams p, InPtrs in, Scratch sc, OutPtrs out) {
+__global__ __launch_bounds__(64) void k_slow_redo(DevParams p, InPtrs in, Scratch sc, OutPtrs out,
+                                                  ZeroRanges z) {
+  zero_ranges(z, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+  if (sc.redo_cnt) {
+    // k_prep_h's list: REDO_LIST_BLOCKS blocks whatever the run's size, the lanes stride over
+    // the entries (any number of them; slow for many, which only force_slow makes).  Each block,
+    // done with the counter, draws a ticket; the last one puts counter and ticket back to zero
+    // for the stream's next prepare.  No block waits for another.
+    const uint32_t cnt = __hip_atomic_load(sc.redo_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) {
+      const uint32_t r = sc.redo_list[i];
+      xof_slow_one<Fp128>(p, in, sc, r);
+      query_h_body<2, PP>(p, in, sc, out, r);
+    }
+    if (threadIdx.x == 0) {  // (one wave per block: its read of the counter is behind it)
+      const uint32_t t = __hip_atomic_fetch_add(sc.redo_cnt + 1, 1u, __ATOMIC_ACQ_REL,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+      if (t == gridDim.x - 1) {
+        __hip_atomic_store(sc.redo_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(sc.redo_cnt + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    return;
+  }
   const uint32_t r0 = (blockIdx.x * blockDim.x + threadIdx.x) * REDO_RPL;
   if (r0 >= p.n || !redo_any(p, sc, r0)) return;
   const uint8_t* fl = sc.flag + r0;
@@ -2041,7 +2081,9 @@ static bool prep_fused_takes(const prio3_engine* e, const DevParams& dp, bool fu
 }
 
 // which query family deferred the slow path of its flagged reports (launch_slow_redo redoes them)
-enum : int { DEFER_NONE = 0, DEFER_QH = 1, DEFER_SUM = 2, DEFER_GEN64 = 3 };
+// DEFER_QH_LIST: k_prep_h, which lists its flagged reports (Scratch::redo_cnt, when not null)
+enum : int { DEFER_NONE = 0, DEFER_QH = 1, DEFER_SUM = 2, DEFER_GEN64 = 3, DEFER_QH_LIST = 4 };
+constexpr uint32_t REDO_LIST_BLOCKS = 32;
 // *deferred: set when a query kernel of this chain skipped flagged reports (slow_defer); the
 // caller then ends the run with launch_slow_redo
 // in.leader_src (executor groups, pulls_in_xof): the leader prep shares are still in the mapped
@@ -2073,6 +2115,7 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
   if (sc.seg) sc.seg += c0;
   if (sc.wseg) sc.wseg += c0 / 64;
   if (sc.wpart) sc.wpart += (size_t)(c0 / 64) * dp.meas_len * 8;
+  sc.redo_c0 = c0;
   const uint32_t blocks = (n + 255) / 256;
   const uint32_t xblocks = (n + XOFD_BLOCK - 1) / XOFD_BLOCK;  // k_prep_h, k_xofd
   if (dp.kind == PRIO3_SUMVEC_F64_MP) {
@@ -2151,6 +2194,7 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
         bool paired = false;
         if (pair)
           TIMED(e, st, "k_prep_hp", (paired = launch_prep_pair(dp, in, sc, out, st, fuse, pl)));
+        if (!paired && deferred) *deferred = DEFER_QH_LIST;
         if (paired) {
         } else if (fuse && pl)
           TIMED(e, st, "k_prep_h", (k_prep_h<true, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
@@ -2208,15 +2252,21 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
   return PRIO3_OK;
 }
 
+// R (nullable): the run, whose fused-aggregate accumulators the k_slow_redo<PP> launch zeroes
 static int launch_slow_redo(prio3_engine* e, const DevParams& base, uint32_t n, InPtrs in,
-                            OutPtrs out, Scratch sc, hipStream_t st, int family) {
+                            OutPtrs out, Scratch sc, hipStream_t st, int family, Run* R) {
+  const bool list = family == DEFER_QH_LIST && sc.redo_cnt;
+  if (family == DEFER_QH_LIST) family = DEFER_QH;
+  if (!list) sc.redo_cnt = nullptr;  // (the pair kernel and k_query_h list nothing)
+  const bool clean = R && R->agg64 && family == DEFER_QH;
+  const ZeroRanges z = clean ? fused_first_zero(R) : ZeroRanges{};
   DevParams dp = base;
   dp.n = n;
   dp.force_slow = (uint32_t)e->force_slow;
   dp.trunc_xof = 0;
   dp.slow_defer = 1;
   dp.redo = 1;
-  const uint32_t g = redo_blocks(n);
+  const uint32_t g = list ? REDO_LIST_BLOCKS : redo_blocks(n);
   if (family == DEFER_GEN64) {  // k_prep_gen<Fp64>: XOF redo, then the generic query
     TIMED(e, st, "k_slow_redo", (k_slow_redo_gen<Fp64><<<g, 64, 0, st>>>(dp, in, sc, out)));
   } else if (family == DEFER_SUM) {
@@ -2227,11 +2277,15 @@ static int launch_slow_redo(prio3_engine* e, const DevParams& base, uint32_t n, 
       default: TIMED(e, st, "k_slow_redo", (k_slow_redo_sum<8><<<g, 64, 0, st>>>(dp, in, sc, out))); break;
     }
   } else if (dp.P == 32)
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<32><<<g, 64, 0, st>>>(dp, in, sc, out)));
+    TIMED(e, st, "k_slow_redo", (k_slow_redo<32><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
   else if (dp.P == 16)
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<16><<<g, 64, 0, st>>>(dp, in, sc, out)));
+    TIMED(e, st, "k_slow_redo", (k_slow_redo<16><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
   else
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<8><<<g, 64, 0, st>>>(dp, in, sc, out)));
+    TIMED(e, st, "k_slow_redo", (k_slow_redo<8><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
+  if (clean) {
+    R->fclean = true;
+    R->fgen = 0;
+  }
   return PRIO3_OK;
 }
 
@@ -2280,6 +2334,17 @@ int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st,
   sc.seg = R->seg;
   sc.wpart = R->wpart;
   sc.wseg = R->wseg;
+  // k_prep_h chains list their flagged reports for the redo launch (in the stream's zero words)
+  // and hold the stream's mutex until the redo launch is enqueued
+  std::unique_lock<std::mutex> zlock;
+  if (R->redo_list && prep_fused_takes(e, R->dp, fuse) && R->dp.kind != PRIO3_SUM) {
+    std::mutex* zmu = nullptr;
+    if (uint32_t* zw = stream_zero_words(R->device, st, &zmu)) {
+      zlock = std::unique_lock<std::mutex>(*zmu);
+      sc.redo_cnt = zw + 1;
+      sc.redo_list = R->redo_list;
+    }
+  }
   R->last = st;
   // small Histogram runs (the executor's groups) on lane pairs: twice the waves, half the work each
   const bool pair = pair_takes(e, R->dp, n, fuse, in.leader_src != nullptr);
@@ -2296,7 +2361,7 @@ int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st,
   if (pair || !allow_chunks || K == 1 || n <= csz || R->dp.kind == PRIO3_FPVEC_BOUNDED_L2) {
     const int rc = launch_prepare(e, R->dp, 0, n, in, out, sc, st, fuse, &deferred, pair);
     if (rc == PRIO3_OK && deferred)
-      return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred);
+      return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred, R);
     return rc;
   }
   int rc = ensure_side_streams(e);
@@ -2313,7 +2378,7 @@ int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st,
     HIPCHK(hipEventRecord(e->side_ev[i], e->side[i]));
     HIPCHK(hipStreamWaitEvent(st, e->side_ev[i], 0));
   }
-  if (deferred) return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred);
+  if (deferred) return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred, R);
   return PRIO3_OK;
 }
 
