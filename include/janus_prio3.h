@@ -482,6 +482,67 @@ int prio3_leader_prepare_next_aggregate_batch(prio3_batch* batch, const uint8_t*
                                               uint8_t* status_inout, const uint32_t* segment_ids,
                                               const uint8_t* accept_mask, uint32_t n_segments,
                                               uint8_t* agg_shares_out, uint64_t* counts_out);
+/* ---- One-call leader job ---- */
+/* What AggregationJobWriter needs from a leader job once the helper's response is decoded
+ * (aggregation_job_driver.rs:629-770, aggregation_job_writer.rs:540-695), in ONE trip through the
+ * prepare_next executor; n is the batch's.  The result is byte for byte this composition, and
+ * every rule of the three calls' sections holds unchanged:
+ *   status[i] = leader_status[i] if it is non-zero, else PRIO3_STATUS_PEER_MISMATCH (5) when
+ *     prepare_error[i] != 0xFF, else 0 (prepare_error NULL: all 0xFF);
+ *   prio3_job_index(report_ids, times, time_precision, closed_intervals, k, max_segments, ...);
+ *   accept[i] = the job index's accept byte AND accept_mask[i] != 0 (NULL mask: all ones);
+ *   prio3_leader_prepare_next_aggregate_batch(batch, prep_msgs, status, segment_ids, accept,
+ *     max_segments, ...);
+ *   prio3_batch_metadata(report_ids, times, status, accept, segment_ids, max_segments, ...);
+ *   outcome[i] = 5 (VdafPrepError) if leader_status[i] != 0, else prepare_error[i] unless that is
+ *     0xFF, else 5 if status[i] != 0, else 0 (BatchCollected) if reject[i] is set, else 0xFF
+ *     (finished) -- a report that already failed keeps its error
+ *     (aggregation_job_writer.rs:577-584).
+ * So rows >= info->n_segments are zero, count 0, Interval::EMPTY; at overflow every segment id is
+ * 0xFFFFFFFF and nothing is counted while statuses stay valid; a duplicate ID marks a report and
+ * rejects nothing; an excluded report still widens its batch's interval; the batch keeps its
+ * output shares (prio3_accumulate over segment_ids and the same accept bytes gives the same
+ * aggregates afterwards).
+ * A job of at most PRIO3_JOB_GROUP_MAX_REPORTS reports and PRIO3_JOB_GROUP_MAX_SEGMENTS segments
+ * on a coalescable engine is indexed by one workgroup in front of the coalesced prepare_next
+ * launch, accumulated behind it and its metadata rows made behind that; such jobs share launches
+ * with each other.  Every other job (empty, larger, FPVec, the multiproof instance, coalesce off)
+ * runs the composition from inside this call -- no size or instance is refused.
+ * The helper's response is decoded in front of the call (janus_dap_agg_job_resp_unpack_host on the
+ * caller's thread); the device decode is not part of it.
+ * out->segment_starts, reject, duplicate, checksums, intervals and outcome may each be NULL;
+ * closed_intervals is read before the call returns.
+ * Errors: those of the three calls (PRIO3_EINVAL for max_segments 0 or above 4096, k > 1024, a
+ * missing buffer), checked before anything is launched. */
+typedef struct {
+  const uint8_t* report_ids;                 /* [n][16] */
+  const uint64_t* times;                     /* [n] */
+  const uint8_t* leader_status;              /* [n]: what prio3_leader_prepare_init_batch wrote */
+  const uint8_t* prepare_error;              /* [n]: what janus_dap_agg_job_resp_unpack_host wrote
+                                                (0xFF = continued); NULL = all 0xFF */
+  const uint8_t* prep_msgs;                  /* [n][prep_msg_len]; NULL without joint randomness */
+  uint64_t time_precision;                   /* 0: a fixed-size task */
+  const uint64_t* closed_intervals;          /* host [k][2] (start, duration); NULL when k = 0 */
+  const uint8_t* accept_mask;                /* host [n], nullable: the replay survivors */
+  uint32_t k;                                /* closed intervals */
+  uint32_t max_segments;
+} prio3_leader_job_in;
+typedef struct {
+  uint32_t* segment_ids;                     /* [n] */
+  uint64_t* segment_starts;                  /* [max_segments], nullable */
+  uint8_t* reject;                           /* [n], nullable */
+  uint8_t* duplicate;                        /* [n], nullable */
+  prio3_job_index_info* info;
+  uint8_t* status;                           /* [n] merged leader status after prepare_next */
+  uint8_t* outcome;                          /* [n], nullable: 0xFF finished, else the DAP
+                                                PrepareError */
+  uint8_t* agg_shares;                       /* [max_segments][agg_share_len] */
+  uint64_t* counts;                          /* [max_segments] */
+  uint8_t* checksums;                        /* [max_segments][32], nullable */
+  uint64_t* intervals;                       /* [max_segments][2], nullable */
+} prio3_leader_job_out;
+int prio3_leader_finish_job(prio3_batch* batch, const prio3_leader_job_in* job,
+                            const prio3_leader_job_out* out);
 int prio3_device_leader_prepare_init(prio3_engine* engine, uint32_t n, const uint8_t* d_nonces,
                                      const uint8_t* d_public_shares,
                                      const uint8_t* d_leader_input_shares, uint8_t* d_prep_shares,

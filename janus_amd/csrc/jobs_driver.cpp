@@ -352,4 +352,102 @@ double janus_jobs_run_job(prio3_engine** engines, int n_engines, const prio3_siz
   });
 }
 
+// A whole leader job as AggregationJobWriter needs it, over the report windows of
+// janus_jobs_run_leader: prio3_leader_prepare_init_batch per job in every form alike, then on the
+// helper's response (msgs[..][prep_msg_len], perr[..] = its prepare_error bytes, times[..]):
+// form 0: the four moves a host-buffer leader makes today -- the per-report overlay of perr on the
+// init status, prio3_job_index, prio3_leader_prepare_next_aggregate_batch over the index's segment
+// ids and accept bytes, prio3_batch_metadata, and the per-report outcome pass; 1:
+// prio3_leader_finish_job; 2: prio3_leader_prepare_next_aggregate_batch alone with one segment and
+// no index, overlay, metadata or outcome (what janus_jobs_run_leader's combined form times).
+// Per job j: seg_out / status_out / reject_out / dup_out / outcome_out [jobs * job_size],
+// ps_out [jobs * job_size][prep_share_len], counts_out [jobs][max_segments], agg_out
+// [jobs][max_segments][agg_len], ck_out [jobs][max_segments][32], iv_out [jobs][max_segments][2],
+// starts_out [jobs][max_segments], info_out [jobs] (form 2 fills status, and row 0 of counts and
+// agg).
+double janus_jobs_run_leader_job(prio3_engine** engines, int n_engines, const prio3_sizes_t* szp,
+                                 int threads, int jobs, int job_size, uint32_t pool,
+                                 const uint8_t* nonces, const uint8_t* pub, const uint8_t* lin,
+                                 const uint8_t* msgs, const uint64_t* times, const uint8_t* perr,
+                                 uint64_t time_precision, const uint64_t* closed, uint32_t k,
+                                 uint32_t max_segments, uint8_t* ps_out, uint32_t* seg_out,
+                                 uint64_t* starts_out, uint8_t* reject_out, uint8_t* dup_out,
+                                 prio3_job_index_info* info_out, uint8_t* status_out,
+                                 uint8_t* outcome_out, uint64_t* counts_out, uint8_t* agg_out,
+                                 uint8_t* ck_out, uint64_t* iv_out, int form) {
+  const prio3_sizes_t sz = *szp;
+  const uint32_t span = pool - (uint32_t)job_size + 1;
+  const size_t S = max_segments;
+  return run_pool(threads, jobs, [&](int j) {
+    thread_local std::vector<uint8_t> acc, ls;
+    const uint32_t t = (uint32_t)(j % n_engines);
+    const size_t r0 = t * (size_t)pool + (((uint64_t)(j / n_engines) * job_size) % span);
+    const size_t o = (size_t)j * job_size;
+    const uint32_t n = (uint32_t)job_size;
+    ls.resize(n);
+    prio3_batch* b = nullptr;
+    int rc = prio3_leader_prepare_init_batch(
+        engines[t], n, nonces + 16 * r0,
+        sz.public_share_len ? pub + (size_t)sz.public_share_len * r0 : nullptr,
+        lin + (size_t)sz.leader_input_share_len * r0, ps_out + (size_t)sz.prep_share_len * o,
+        ls.data(), &b);
+    const uint8_t* m = sz.prep_msg_len ? msgs + (size_t)sz.prep_msg_len * r0 : nullptr;
+    const uint8_t* pe = perr + r0;
+    uint8_t* st = status_out + o;
+    uint8_t* agg = agg_out + (size_t)sz.agg_share_len * S * j;
+    uint64_t* cnt = counts_out + S * j;
+    if (rc == PRIO3_OK && form == 2) {
+      memcpy(st, ls.data(), n);
+      rc = prio3_leader_prepare_next_aggregate_batch(b, m, st, nullptr, nullptr, 1, agg, cnt);
+    } else if (rc == PRIO3_OK && form == 1) {
+      prio3_leader_job_in in{};
+      in.report_ids = nonces + 16 * r0;
+      in.times = times + r0;
+      in.leader_status = ls.data();
+      in.prepare_error = pe;
+      in.prep_msgs = m;
+      in.time_precision = time_precision;
+      in.closed_intervals = closed;
+      in.k = k;
+      in.max_segments = max_segments;
+      prio3_leader_job_out out{};
+      out.segment_ids = seg_out + o;
+      out.segment_starts = starts_out + S * j;
+      out.reject = reject_out + o;
+      out.duplicate = dup_out + o;
+      out.info = info_out + j;
+      out.status = st;
+      out.outcome = outcome_out + o;
+      out.agg_shares = agg;
+      out.counts = cnt;
+      out.checksums = ck_out + 32 * S * j;
+      out.intervals = iv_out + 2 * S * j;
+      rc = prio3_leader_finish_job(b, &in, &out);
+    } else if (rc == PRIO3_OK) {
+      acc.resize(n);
+      for (uint32_t i = 0; i < n; i++)  // the helper's prepare_error over the init status
+        st[i] = ls[i] ? ls[i] : pe[i] != 0xFF ? (uint8_t)PRIO3_STATUS_PEER_MISMATCH : 0;
+      rc = prio3_job_index(engines[t], n, nonces + 16 * r0, times + r0, time_precision, closed, k,
+                           max_segments, seg_out + o, starts_out + S * j, acc.data(),
+                           reject_out + o, dup_out + o, info_out + j);
+      if (rc == PRIO3_OK)
+        rc = prio3_leader_prepare_next_aggregate_batch(b, m, st, seg_out + o, acc.data(),
+                                                       max_segments, agg, cnt);
+      if (rc == PRIO3_OK)
+        rc = prio3_batch_metadata(engines[t], n, nonces + 16 * r0, times + r0, st, acc.data(),
+                                  seg_out + o, max_segments, ck_out + 32 * S * j,
+                                  iv_out + 2 * S * j);
+      for (uint32_t i = 0; rc == PRIO3_OK && i < n; i++) {  // the outcome byte
+        uint8_t oc = pe[i];
+        if (oc == 0xFF && st[i] != 0) oc = 5;
+        if (ls[i] != 0) oc = 5;
+        if (oc == 0xFF && reject_out[o + i]) oc = 0;
+        outcome_out[o + i] = oc;
+      }
+    }
+    if (b) prio3_batch_free(b);
+    return rc == PRIO3_OK;
+  });
+}
+
 }  // extern "C"

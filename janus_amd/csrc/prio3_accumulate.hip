@@ -1006,21 +1006,22 @@ int fused_finish(prio3_engine* e, Run* R, const uint8_t* d_status, const uint32_
 
 // On failure the stream is drained and the area released here.
 Slab* acc_multi_enqueue(int device, uint32_t es, uint8_t* host, const AccLayout& L,
-                        uint32_t n_jobs, size_t out_bytes, hipStream_t st, int* rc) {
+                        uint32_t n_jobs, size_t out_bytes, hipStream_t st, int* rc, Slab* area) {
   const AccDesc* D = (const AccDesc*)(host + L.desc_off);
   uint32_t reps = 0, max_len = 0;
   for (uint32_t i = 0; i < n_jobs; i++) {
     reps = std::max(reps, (uint32_t)((D[i].acc_off - L.acc_off) + D[i].n));
     max_len = std::max(max_len, D[i].out_len);
   }
-  Slab* sl = ws_acquire(device, L.bytes, st, rc);
+  Slab* sl = area ? area : ws_acquire(device, L.bytes, st, rc);
   if (!sl) return nullptr;
   uint8_t* b = sl->base;
   auto h2d = [&](size_t off, size_t bytes) {
     return hipMemcpyAsync(b + off, host + off, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
   };
-  bool ok = h2d(L.desc_off, sizeof(AccDesc) * n_jobs) && h2d(L.seg_off, 4 * (size_t)reps) &&
-            h2d(L.acc_off, reps);
+  // (a caller's area holds the segment ids and accept bytes already: the staging's stay out)
+  bool ok = h2d(L.desc_off, sizeof(AccDesc) * n_jobs) &&
+            (area || (h2d(L.seg_off, 4 * (size_t)reps) && h2d(L.acc_off, reps)));
   if (ok) {
     by_field(es, [&](auto f) -> int {
       k_acc_multi<decltype(f)><<<dim3(max_len, n_jobs), 256, 0, st>>>(

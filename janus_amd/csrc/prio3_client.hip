@@ -1293,9 +1293,15 @@ __global__ __launch_bounds__(256) void k_leader_next(DevParams p, const uint8_t*
 // job y (its descriptor, prepare messages and statuses in the executor's mapped staging); the
 // verdict goes back to the staging and to the run's device statuses (which prio3_accumulate
 // reads).  Same per-report work as k_leader_next.
-template <class F>
+// JIX: a group of prio3_leader_finish_job jobs.  The staged status is the leader's init status and
+// the helper's prepare_error is laid over it first (a report the helper failed or finished early
+// is a PeerMessageMismatch unless the leader had failed it already); the merged status also goes
+// to a contiguous device array for the metadata launch, and the outcome byte is made here, from
+// the merged status and the reject byte the index kernel left in device memory.
+template <class F, bool JIX>
 __global__ __launch_bounds__(256) void k_leader_next_multi(const LNextDesc* descs,
-                                                           const uint8_t* msgs, uint8_t* status) {
+                                                           const uint8_t* msgs, uint8_t* status,
+                                                           LNextJixPtrs J) {
   typedef typename F::T T;
   __shared__ LNextDesc D;
   if (threadIdx.x == 0) D = descs[blockIdx.y];
@@ -1304,6 +1310,12 @@ __global__ __launch_bounds__(256) void k_leader_next_multi(const LNextDesc* desc
   if (r >= D.n) return;
   const size_t g = (size_t)D.rep_off + r, ld = D.ld;
   uint8_t st = status[g];
+  uint8_t init_st = 0, pe = 0xFF;
+  if (JIX) {
+    init_st = st;
+    pe = J.perr[g];
+    if (st == PRIO3_STATUS_FINISHED && pe != 0xFF) st = PRIO3_STATUS_PEER_MISMATCH;
+  }
   if (st == PRIO3_STATUS_FINISHED && D.jr) {
     uint32_t m[4];
     load16(msgs + 16 * g, m);
@@ -1312,6 +1324,16 @@ __global__ __launch_bounds__(256) void k_leader_next_multi(const LNextDesc* desc
   }
   status[g] = st;
   D.dstatus[r] = st;
+  if (JIX) {
+    J.mstatus[g] = st;
+    // VdafPrepError for the leader's own failures, else the helper's error, else BatchCollected
+    // for a report of a closed batch that had not failed (aggregation_job_writer.rs:577-584)
+    uint8_t o = pe;
+    if (o == 0xFF && st != PRIO3_STATUS_FINISHED) o = 5;
+    if (init_st != PRIO3_STATUS_FINISHED) o = 5;
+    if (o == 0xFF && J.drej[g]) o = 0;
+    J.outcome[g] = o;
+  }
   if (D.kind == PRIO3_SUM || D.kind == PRIO3_SUMVEC) {
     const uint32_t outs = D.kind == PRIO3_SUM ? 1 : D.out_len;
     for (uint32_t e = 0; e < outs; e++) {
@@ -1327,12 +1349,21 @@ __global__ __launch_bounds__(256) void k_leader_next_multi(const LNextDesc* desc
 
 extern "C" int launch_leader_next_multi(uint32_t es, const LNextDesc* d_desc, const uint8_t* d_msgs,
                                         uint8_t* d_status, uint32_t n_jobs, uint32_t max_n,
-                                        hipStream_t st) {
+                                        hipStream_t st, const LNextJixPtrs* jix) {
   const dim3 grid((max_n + 255) / 256, n_jobs);
-  if (es == 16)
-    k_leader_next_multi<Fp128><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status);
-  else
-    k_leader_next_multi<Fp64><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status);
+  if (jix) {
+    if (!jix->perr || !jix->drej || !jix->mstatus || !jix->outcome) return PRIO3_EINVAL;
+    if (es == 16)
+      k_leader_next_multi<Fp128, true><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status, *jix);
+    else
+      k_leader_next_multi<Fp64, true><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status, *jix);
+  } else if (es == 16) {
+    k_leader_next_multi<Fp128, false><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status,
+                                                            LNextJixPtrs{});
+  } else {
+    k_leader_next_multi<Fp64, false><<<grid, 256, 0, st>>>(d_desc, d_msgs, d_status,
+                                                           LNextJixPtrs{});
+  }
   return hipGetLastError() == hipSuccess ? PRIO3_OK : PRIO3_EDEVICE;
 }
 

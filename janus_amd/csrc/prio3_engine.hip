@@ -1031,6 +1031,9 @@ static size_t acc_out_bytes(const Run* R, uint32_t nseg) {
   const size_t agg = (size_t)R->dp.out_len * R->dp.es * nseg;
   return ((agg + 7) & ~(size_t)7) + 8 * (size_t)nseg;
 }
+// an indexed prepare_next job: its segment ids and accept bytes are made on the device
+static bool acc_indexed(const AccJob*) { return false; }
+static bool acc_indexed(const LNextJob* j) { return j->jix; }
 template <class Job>
 static void acc_stage(const Job* j, uint32_t slot, uint8_t* area, const AccLayout& L) {
   const Run* R = j->run;
@@ -1046,6 +1049,10 @@ static void acc_stage(const Job* j, uint32_t slot, uint8_t* area, const AccLayou
   D.acc_off = L.acc_off + j->rep_off;
   D.agg_off = L.out_off + j->out_off;
   D.cnt_off = D.agg_off + acc_out_bytes(R, j->nseg) - 8 * (size_t)j->nseg;
+  if (acc_indexed(j)) {  // the group's index kernel writes both ranges in the device area
+    D.flags = 3u;
+    return;
+  }
   if (j->seg) memcpy(area + D.seg_off, j->seg, 4 * (size_t)j->n);
   if (j->accept) memcpy(area + D.acc_off, j->accept, j->n);
 }
@@ -1166,7 +1173,7 @@ int engine_leader_issue(prio3_engine* lead, const LeaderLayout& L, uint8_t* stg,
   return PRIO3_OK;
 }
 
-uint32_t engine_lnext_key(const LNextJob* j) { return j->run->dp.es; }
+uint32_t engine_lnext_key(const LNextJob* j) { return j->run->dp.es | (j->jix ? 0x100u : 0u); }
 
 void engine_lnext_stage(LNextJob* j, uint8_t* stg, const LNextLayout& L) {
   const Run* R = j->run;
@@ -1189,6 +1196,33 @@ void engine_lnext_stage(LNextJob* j, uint8_t* stg, const LNextLayout& L) {
   // its accumulate descriptor (offsets from the accumulate area's base; the verdicts it reads
   // are those of the check in the same launch)
   if (j->nseg) acc_stage(j, j->acc_slot, stg + L.acc_base, L.acc);
+  if (!j->jix) return;
+  // the index request: IDs, times, the helper's prepare_error and the host's accept bytes by
+  // report; the job's descriptor and closed intervals, read here, before the call returns
+  const size_t r0 = j->rep_off, n = j->n;
+  memcpy(stg + L.id_off + 16 * r0, j->ids, 16 * n);
+  memcpy(stg + L.time_off + 8 * r0, j->times, 8 * n);
+  if (j->perr)
+    memcpy(stg + L.perr_off + r0, j->perr, n);
+  else
+    memset(stg + L.perr_off + r0, 0xff, n);
+  if (j->accept)
+    memcpy(stg + L.hacc_off + r0, j->accept, n);
+  else
+    memset(stg + L.hacc_off + r0, 1, n);
+  JixJobDesc jd;
+  jd.c0 = j->rep_off;
+  jd.n = j->n;
+  jd.pad0 = j->rep_off;
+  jd.end = j->rep_off + j->n;
+  jd.seg0 = j->seg0;
+  jd.max_segments = j->nseg;
+  jd.closed0 = j->closed0;
+  jd.k = j->precision ? j->nclosed : 0;
+  jd.precision = j->precision;
+  memcpy(stg + L.jdesc_off + sizeof(JixJobDesc) * j->jslot, &jd, sizeof jd);
+  if (j->nclosed)
+    memcpy(stg + L.jclosed_off + 16 * (size_t)j->closed0, j->closed, 16 * (size_t)j->nclosed);
 }
 
 size_t engine_lnext_out_bytes(const LNextJob* j) {
@@ -1198,17 +1232,144 @@ size_t engine_lnext_out_bytes(const LNextJob* j) {
 void engine_lnext_unstage(LNextJob* j, const uint8_t* stg, const LNextLayout& L) {
   memcpy(j->status, stg + L.status_off + j->rep_off, j->n);
   if (j->nseg) acc_unstage(j, j->acc_slot, stg + L.acc_base, L.acc);
+  if (!j->jix) return;
+  const size_t r0 = j->rep_off, n = j->n, s0 = j->seg0, S = j->nseg;
+  memcpy(j->jseg_out, stg + L.jseg_off + 4 * r0, 4 * n);
+  if (j->jrej_out) memcpy(j->jrej_out, stg + L.jrej_off + r0, n);
+  if (j->jdup_out) memcpy(j->jdup_out, stg + L.jdup_off + r0, n);
+  if (j->outcome_out) memcpy(j->outcome_out, stg + L.outcome_off + r0, n);
+  // a fixed-size task has no starts: the caller's array is left as it is (prio3_job_index)
+  if (j->jstarts_out && j->precision) memcpy(j->jstarts_out, stg + L.jstart_off + 8 * s0, 8 * S);
+  memcpy(j->jinfo_out, stg + L.jinfo_off + sizeof(prio3_job_index_info) * j->jslot,
+         sizeof(prio3_job_index_info));
+  if (j->ck_out) memcpy(j->ck_out, stg + L.ck_off + 32 * s0, 32 * S);
+  if (j->iv_out) memcpy(j->iv_out, stg + L.iv_off + 16 * s0, 16 * S);
+}
+
+void engine_lnext_collect(prio3_engine* lead) {
+  if (lead && lead->timing) collect_times(lead, false);
+}
+
+// The launches of an indexed group (prio3_leader_finish_job), in stream order -- the only
+// ordering: k_jix_lgroup (group segment ids, accept and reject bytes into device memory, the
+// index outputs into the staging), the check with the prepare_error overlay, k_acc_multi over the
+// index's ids and accept bytes, the metadata launch over the group's contiguous reports.
+static int lnext_issue_indexed(int device, uint32_t es, uint8_t* stg, uint8_t* stg_dev,
+                               const LNextLayout& L, uint32_t n_jobs, uint32_t max_n,
+                               uint32_t n_acc, size_t out_bytes, hipStream_t st,
+                               const LNextJixGroup& jg, Slab** slab_out, Slab** slab2_out) {
+  prio3_engine* e = jg.e;
+  if (!L.jix || n_acc != n_jobs || jg.njix != n_jobs || !jg.reps || !jg.nseg ||
+      jg.reps > LNEXT_MAX_REPS || jg.nseg > EXEC_MAX_SEGS)
+    return PRIO3_EINVAL;
+  LNextJixDev V;
+  lnext_jix_dev_layout(&V);
+  int rc = PRIO3_OK;
+  Slab* area = ws_acquire(device, L.acc.bytes, st, &rc);
+  if (!area) return rc;
+  Slab* dev = ws_acquire(device, V.bytes, st, &rc);
+  if (!dev) {
+    ws_release(area, st);
+    return rc;
+  }
+  uint8_t *ab = area->base, *db = dev->base;
+  const uint8_t* hd = stg_dev;
+  rc = [&]() -> int {
+    JixGroupArgs a{};
+    a.desc = (const JixJobDesc*)(hd + L.jdesc_off);
+    a.closed = (const unsigned long long*)(hd + L.jclosed_off);
+    a.ids = hd + L.id_off;
+    a.times = (const unsigned long long*)(hd + L.time_off);
+    a.accept = hd + L.hacc_off;
+    a.ids_dev = db + V.ids_off;
+    a.gseg = (uint32_t*)(db + V.gseg_off);
+    a.gaccept = ab + L.acc.acc_off;
+    a.seg_out = (uint32_t*)(stg_dev + L.jseg_off);
+    a.rej_out = stg_dev + L.jrej_off;
+    a.dup_out = stg_dev + L.jdup_off;
+    a.starts_out = (unsigned long long*)(stg_dev + L.jstart_off);
+    a.info_out = (prio3_job_index_info*)(stg_dev + L.jinfo_off);
+    a.lseg = (uint32_t*)(ab + L.acc.seg_off);
+    a.drej = db + V.rej_off;
+    int r = launch_jix_group(e, n_jobs, a, st, true);
+    if (r) return r;
+    LNextJixPtrs jp;
+    jp.perr = hd + L.perr_off;
+    jp.drej = db + V.rej_off;
+    jp.mstatus = db + V.mstatus_off;
+    jp.outcome = stg_dev + L.outcome_off;
+    TIMED(e, st, "k_leader_next_multi",
+          (r = launch_leader_next_multi(es, (const LNextDesc*)(hd + L.desc_off), hd + L.msg_off,
+                                        stg_dev + L.status_off, n_jobs, max_n, st, &jp)));
+    return r;
+  }();
+  if (rc == PRIO3_OK) {
+    // (on failure acc_multi_enqueue has drained the stream and released the area)
+    Slab* got = nullptr;
+    const int r2 = [&]() -> int {
+      int r = PRIO3_OK;
+      TIMED(e, st, "k_acc_multi",
+            (got = acc_multi_enqueue(device, es, stg + L.acc_base, L.acc, n_acc, out_bytes, st, &r,
+                                     area)));
+      return r;
+    }();
+    if (!got) {
+      ws_release(dev, st);
+      return r2 ? r2 : PRIO3_EDEVICE;
+    }
+  } else {
+    (void)hipStreamSynchronize(st);
+    ws_release(area, st);
+    ws_release(dev, st);
+    return rc;
+  }
+  // the rest of the BatchAggregation update over the group's reports and segments, from the merged
+  // statuses in device memory; the rows go back into the staging
+  rc = launch_batch_metadata(e, jg.reps, db + V.ids_off, (const uint64_t*)(hd + L.time_off),
+                             db + V.mstatus_off, ab + L.acc.acc_off,
+                             (const uint32_t*)(db + V.gseg_off), jg.nseg,
+                             (uint32_t*)(db + V.ck_off), (unsigned long long*)(db + V.iv_off), st);
+  if (rc == PRIO3_OK &&
+      (hipMemcpyAsync(stg + L.ck_off, db + V.ck_off, 32 * (size_t)jg.nseg, hipMemcpyDeviceToHost,
+                      st) != hipSuccess ||
+       hipMemcpyAsync(stg + L.iv_off, db + V.iv_off, 16 * (size_t)jg.nseg, hipMemcpyDeviceToHost,
+                      st) != hipSuccess))
+    rc = PRIO3_EDEVICE;
+  if (rc != PRIO3_OK) {
+    (void)hipStreamSynchronize(st);
+    ws_release(area, st);
+    ws_release(dev, st);
+    return rc;
+  }
+  *slab_out = area;
+  *slab2_out = dev;
+  return PRIO3_OK;
 }
 
 int engine_lnext_issue(int device, uint32_t es, uint8_t* stg, uint8_t* stg_dev,
                        const LNextLayout& L, uint32_t n_jobs, uint32_t max_n, uint32_t n_acc,
-                       size_t out_bytes, hipStream_t* st_out, Slab** slab_out, bool own_queue) {
+                       size_t out_bytes, hipStream_t* st_out, Slab** slab_out, bool own_queue,
+                       const LNextJixGroup* jg, Slab** slab2_out) {
   *st_out = nullptr;
   *slab_out = nullptr;
+  if (slab2_out) *slab2_out = nullptr;
   DeviceGuard dg_(device);
   HIPCHK(dg_.rc);
   hipStream_t st = own_queue ? ws_exec_stream_get(device) : ws_stream_get(device);
   if (!st) return PRIO3_EDEVICE;
+  if (jg && jg->e) {
+    const int rc = !slab2_out ? PRIO3_EINVAL
+                              : lnext_issue_indexed(device, es, stg, stg_dev, L, n_jobs, max_n,
+                                                    n_acc, out_bytes, st, *jg, slab_out, slab2_out);
+    if (rc != PRIO3_OK) {
+      (void)hipStreamSynchronize(st);
+      (void)hipGetLastError();
+      ws_exec_stream_put(device, st);
+      return rc;
+    }
+    *st_out = st;
+    return PRIO3_OK;
+  }
   int rc = launch_leader_next_multi(es, (const LNextDesc*)(stg_dev + L.desc_off),
                                     stg_dev + L.msg_off, stg_dev + L.status_off, n_jobs, max_n, st);
   Slab* sl = nullptr;
@@ -2401,6 +2562,99 @@ int prio3_leader_prepare_next_aggregate_batch(prio3_batch* b, const uint8_t* pre
   if (rc == PRIO3_OK)
     rc = prio3_accumulate(b, segment_ids, accept_mask, n_segments, agg_shares_out, counts_out);
   return rc;
+}
+
+// The composition prio3_leader_finish_job stands for, as a caller would make it: what a job
+// outside the in-group path runs, and what every other job's result equals.
+static int leader_job_composition(prio3_batch* b, const prio3_leader_job_in& in,
+                                  const prio3_leader_job_out& out) {
+  prio3_engine* e = b->e;
+  const uint32_t n = b->n, S = in.max_segments;
+  std::vector<uint8_t> acc(n ? n : 1);
+  for (uint32_t i = 0; i < n; i++) {  // the helper's prepare_error laid over the init status
+    const uint8_t ls = in.leader_status[i], pe = in.prepare_error ? in.prepare_error[i] : 0xFF;
+    out.status[i] = ls ? ls : pe != 0xFF ? (uint8_t)PRIO3_STATUS_PEER_MISMATCH : 0;
+  }
+  std::vector<uint8_t> rej(n ? n : 1);
+  int rc = prio3_job_index(e, n, in.report_ids, in.times, in.time_precision, in.closed_intervals,
+                           in.k, S, out.segment_ids, out.segment_starts, acc.data(), rej.data(),
+                           out.duplicate, out.info);
+  if (rc) return rc;
+  if (in.accept_mask)
+    for (uint32_t i = 0; i < n; i++) acc[i] = acc[i] && in.accept_mask[i];
+  uint8_t none = 0;  // an empty job may come without a status array
+  rc = prio3_leader_prepare_next_aggregate_batch(b, in.prep_msgs, n ? out.status : &none,
+                                                 out.segment_ids, acc.data(), S, out.agg_shares,
+                                                 out.counts);
+  if (rc) return rc;
+  if (out.checksums || out.intervals) {
+    rc = prio3_batch_metadata(e, n, in.report_ids, in.times, out.status, acc.data(),
+                              out.segment_ids, S, out.checksums, out.intervals);
+    if (rc) return rc;
+  }
+  if (out.reject && n) memcpy(out.reject, rej.data(), n);
+  if (out.outcome)
+    for (uint32_t i = 0; i < n; i++) {
+      uint8_t o = in.prepare_error ? in.prepare_error[i] : 0xFF;
+      if (o == 0xFF && out.status[i] != PRIO3_STATUS_FINISHED) o = 5;  // VdafPrepError
+      if (in.leader_status[i] != PRIO3_STATUS_FINISHED) o = 5;
+      if (o == 0xFF && rej[i]) o = 0;  // BatchCollected, unless the report had failed already
+      out.outcome[i] = o;
+    }
+  return PRIO3_OK;
+}
+
+// process_response_from_helper's per-report work and the writer's bookkeeping for one leader job
+// (aggregation_job_driver.rs:629-770, aggregation_job_writer.rs:540-695) in one trip through the
+// prepare_next executor: index, overlay + check, accumulate, metadata.
+int prio3_leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
+                            const prio3_leader_job_out* out) {
+  TraceSpan span_("leader VDAF preparation");
+  if (!b || !in || !out || !out->info) return PRIO3_EINVAL;
+  prio3_engine* e = b->e;
+  const uint32_t n = b->n, S = in->max_segments;
+  const DevParams& d = e->dp;
+  // the argument rules of the three calls, checked before any of them runs
+  if (n > (1u << 30) || S == 0 || S > 4096 || in->k > 1024 || (in->k && !in->closed_intervals) ||
+      !out->agg_shares || !out->counts ||
+      (n && (!in->report_ids || !in->times || !in->leader_status || !out->status ||
+             !out->segment_ids)))
+    return PRIO3_EINVAL;
+  Run* R = b->run;
+  if (n && R && d.jr_len && !in->prep_msgs) return PRIO3_EINVAL;
+  LNextJob job;
+  job.device = e->device;
+  job.run = R;
+  job.nseg = S;
+  const bool group = R && n && n <= JIX_GROUP_MAX_N && S <= JIX_GROUP_MAX_SEG &&
+                     leader_coalescable(e) && R->msgs && R->linput &&
+                     engine_lnext_out_bytes(&job) <= LNEXT_MAX_OUT;
+  if (!group) return leader_job_composition(b, *in, *out);
+  memcpy(out->status, in->leader_status, n);  // in/out: the overlay is the kernel's
+  job.c0 = b->c0;
+  job.n = n;
+  job.msgs = d.jr_len ? in->prep_msgs : nullptr;
+  job.status = out->status;
+  job.accept = in->accept_mask;
+  job.agg_out = out->agg_shares;
+  job.counts_out = out->counts;
+  job.jix = true;
+  job.e = e;
+  job.ids = in->report_ids;
+  job.times = in->times;
+  job.perr = in->prepare_error;
+  job.precision = in->time_precision;
+  job.closed = in->closed_intervals;
+  job.nclosed = in->k;
+  job.jseg_out = out->segment_ids;
+  job.jstarts_out = out->segment_starts;
+  job.jrej_out = out->reject;
+  job.jdup_out = out->duplicate;
+  job.jinfo_out = out->info;
+  job.outcome_out = out->outcome;
+  job.ck_out = out->checksums;
+  job.iv_out = out->intervals;
+  return exec_leader_next(&job);
 }
 
 int prio3_trace_enabled(void) { return trace_enabled() ? 1 : 0; }

@@ -163,8 +163,12 @@ int fused_finish(prio3_engine* e, Run* R, const uint8_t* d_status, const uint32_
 // `host` as AccLayout lays them out) enqueued on st: the staged inputs into a device area from
 // the scratch pool, k_acc_multi, the first out_bytes of the outputs back into `host`.  Returns
 // the area (the caller releases it after the stream), or nullptr with *rc set.
+// area (optional): the device area, acquired by the caller and already holding the group's segment
+// ids and accept bytes (an indexed prepare_next group: its index kernel wrote them) -- then only
+// the descriptors are copied in, so the staging's unset ids never land on them.
 Slab* acc_multi_enqueue(int device, uint32_t es, uint8_t* host, const AccLayout& L,
-                        uint32_t n_jobs, size_t out_bytes, hipStream_t st, int* rc);
+                        uint32_t n_jobs, size_t out_bytes, hipStream_t st, int* rc,
+                        Slab* area = nullptr);
 int launch_combine(prio3_engine* e, uint32_t k, uint32_t n_segments, const uint8_t* d_in,
                    const uint64_t* d_counts_in, uint8_t* d_out, uint64_t* d_counts_out,
                    hipStream_t st);
@@ -196,8 +200,15 @@ struct JixGroupArgs {
   uint8_t *rej_out, *dup_out;
   unsigned long long* starts_out;
   prio3_job_index_info* info_out;
+  // k_jix_lgroup (a group of prio3_leader_finish_job jobs, columns = the group's report offsets,
+  // no pad columns): the job-local segment ids k_acc_multi reads and the reject bytes the check
+  // reads for the outcome, both in device memory
+  uint32_t* lseg = nullptr;
+  uint8_t* drej = nullptr;
 };
-int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st);
+// leader: k_jix_lgroup (the same device body, plus lseg / drej)
+int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st,
+                     bool leader = false);
 
 // ---- prio3_client.hip: the generic leader kernels ----
 extern "C" int launch_leader_init(const DevParams& dp, const uint8_t* d_nonces,
@@ -206,6 +217,17 @@ extern "C" int launch_leader_init(const DevParams& dp, const uint8_t* d_nonces,
                                   hipStream_t st, const uint16_t* vk_slot, const uint4* vk_tab);
 extern "C" int launch_leader_next(const DevParams& dp, const uint8_t* d_prep_msgs,
                                   const Scratch& sc, uint8_t* d_status, hipStream_t st);
+// What the check of an indexed group (prio3_leader_finish_job) reads and writes beside the
+// staging's statuses, per report of the group: perr the staged prepare_error bytes, drej the index
+// kernel's reject bytes (device), mstatus the merged statuses for the metadata launch (device),
+// outcome the staged outcome bytes.
+struct LNextJixPtrs {
+  const uint8_t* perr = nullptr;
+  const uint8_t* drej = nullptr;
+  uint8_t* mstatus = nullptr;
+  uint8_t* outcome = nullptr;
+};
 extern "C" int launch_leader_next_multi(uint32_t es, const LNextDesc* d_desc,
                                         const uint8_t* d_msgs, uint8_t* d_status, uint32_t n_jobs,
-                                        uint32_t max_n, hipStream_t st);
+                                        uint32_t max_n, hipStream_t st,
+                                        const LNextJixPtrs* jix = nullptr);

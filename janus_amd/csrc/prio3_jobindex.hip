@@ -368,7 +368,12 @@ constexpr uint32_t JIXG_SLOTS = 2 * JIX_GROUP_MAX_N;   // 32 KiB of report indic
 constexpr uint32_t JIXG_TAB = 4 * JIX_GROUP_MAX_SEG;   // start table (2 KiB)
 constexpr uint32_t JIXG_KEYS = 2 * JIX_GROUP_MAX_SEG;  // sorted starts, padded to a power of two
 
-__global__ __launch_bounds__(JIXG_T) void k_jix_group(JixGroupArgs A) {
+// LEADER: the sibling for groups of prio3_leader_finish_job jobs (k_jix_lgroup) -- the columns are
+// the group's report offsets (no pad columns: pad0 = c0, end = c0 + n), and each report also gets
+// its job-local segment id in A.lseg (what k_acc_multi reads beside A.gaccept) and its reject byte
+// in A.drej (what the check reads for the outcome), both in device memory.
+template <bool LEADER>
+__device__ __forceinline__ void jix_group_body(const JixGroupArgs& A) {
   __shared__ uint32_t s_slot[JIXG_SLOTS];
   __shared__ unsigned long long s_tab[JIXG_TAB];
   __shared__ unsigned long long s_key[JIXG_KEYS];
@@ -524,6 +529,10 @@ __global__ __launch_bounds__(JIXG_T) void k_jix_group(JixGroupArgs A) {
       A.seg_out[c] = seg;
       A.rej_out[c] = closed ? PRIO3_REJECT_BATCH_COLLECTED : 0;
       A.dup_out[c] = dup;
+      if (LEADER) {
+        A.lseg[c] = seg;
+        A.drej[c] = closed ? PRIO3_REJECT_BATCH_COLLECTED : 0;
+      }
     }
     const unsigned long long m_dup = __ballot(dup), m_closed = __ballot(closed),
                              m_err = __ballot(time_error);
@@ -548,6 +557,9 @@ __global__ __launch_bounds__(JIXG_T) void k_jix_group(JixGroupArgs A) {
     A.info_out[blockIdx.x] = info;
   }
 }
+
+__global__ __launch_bounds__(JIXG_T) void k_jix_group(JixGroupArgs A) { jix_group_body<false>(A); }
+__global__ __launch_bounds__(JIXG_T) void k_jix_lgroup(JixGroupArgs A) { jix_group_body<true>(A); }
 
 uint32_t next_pow2(uint64_t v) {
   uint64_t p = 1;
@@ -634,11 +646,17 @@ int prio3_device_job_index(prio3_engine* e, uint32_t n, const uint8_t* d_report_
   return rc;
 }
 
-int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st) {
+int launch_jix_group(prio3_engine* e, uint32_t n_jobs, const JixGroupArgs& a, hipStream_t st,
+                     bool leader) {
   static_assert(JIX_GROUP_MAX_N == PRIO3_JOB_GROUP_MAX_REPORTS &&
                     JIX_GROUP_MAX_SEG == PRIO3_JOB_GROUP_MAX_SEGMENTS,
                 "the header's limits are the kernel's");
   if (!n_jobs) return PRIO3_OK;
+  if (leader) {
+    if (!a.lseg || !a.drej) return PRIO3_EINVAL;
+    TIMED(e, st, "k_jix_lgroup", (k_jix_lgroup<<<n_jobs, JIXG_T, 0, st>>>(a)));
+    return PRIO3_OK;
+  }
   TIMED(e, st, "k_jix_group", (k_jix_group<<<n_jobs, JIXG_T, 0, st>>>(a)));
   return PRIO3_OK;
 }

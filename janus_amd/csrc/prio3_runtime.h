@@ -356,6 +356,28 @@ struct LNextJob {
   uint32_t slot = 0, rep_off = 0;  // placement in the group
   uint32_t acc_slot = 0;           // its accumulate descriptor (aggregating jobs)
   size_t out_off = 0;              // its aggregate shares + counts in the accumulate area
+  // prio3_leader_finish_job: the group's launch makes the job's index itself (k_jix_lgroup, in
+  // front of the check), overlays the helper's prepare_error on the statuses, and makes the batch
+  // metadata behind the accumulate -- `seg` is not read, `accept` is the host's replay mask, nseg
+  // is the job's max_segments, `status` holds the leader's init statuses on entry
+  bool jix = false;
+  prio3_engine* e = nullptr;         // the batch's engine (timing events of the group's launches)
+  const uint8_t* ids = nullptr;      // host [n][16]
+  const uint64_t* times = nullptr;   // host [n]
+  const uint8_t* perr = nullptr;     // host [n] prepare_error (nullable: all 0xFF)
+  uint64_t precision = 0;            // time_precision (0: a fixed-size task)
+  const uint64_t* closed = nullptr;  // host [nclosed][2] (start, duration), read by stage()
+  uint32_t nclosed = 0;
+  uint32_t* jseg_out = nullptr;      // host outputs of the index: [n] job-local segment ids,
+  uint64_t* jstarts_out = nullptr;   // [nseg] (nullable), [n] reject / duplicate (nullable), info
+  uint8_t *jrej_out = nullptr, *jdup_out = nullptr;
+  void* jinfo_out = nullptr;         // prio3_job_index_info
+  uint8_t* outcome_out = nullptr;    // host [n] (nullable)
+  uint8_t* ck_out = nullptr;         // host [nseg][32] (nullable)
+  uint64_t* iv_out = nullptr;        // host [nseg][2] (nullable)
+  uint32_t jslot = 0;    // the job's descriptor in its group
+  uint32_t closed0 = 0;  // its first row of the group's closed-interval table
+  uint32_t seg0 = 0;     // its first segment among the group's
 };
 // one per job of a prepare_next group (read by the kernel from the mapped staging)
 struct LNextDesc {
@@ -369,23 +391,52 @@ struct LNextDesc {
 constexpr uint32_t LNEXT_MAX_JOBS = 1024, LNEXT_MAX_REPS = 1u << 17;
 constexpr size_t LNEXT_MAX_OUT = (size_t)32 << 20;  // aggregate shares + counts per group
 // the staging of a prepare_next group: descriptors, messages, statuses, then (aggregating jobs)
-// an accumulate area laid out as an accumulate group's (acc_layout) from acc_base
+// an accumulate area laid out as an accumulate group's (acc_layout) from acc_base.
+// Groups of jobs that carry an index request (LNextJob::jix) also stage, per report, the ID [16],
+// the time (u64), prepare_error and the host accept byte, and receive the job-local segment id
+// (u32), reject, duplicate and outcome bytes; per job a JixJobDesc, its rows of the
+// closed-interval table [JIX_GROUP_CLOSED][2] and the info struct (6 x u32); per group segment
+// (EXEC_MAX_SEGS) the start (u64), checksum [32] and interval [2] (u64).  The group's device
+// area (LNextJixDev, from the scratch pool) follows the same per-report order.
 struct LNextLayout {
   size_t desc_off, msg_off, status_off, acc_base, bytes;
   AccLayout acc;
+  bool jix = false;
+  size_t id_off = 0, time_off = 0, perr_off = 0, hacc_off = 0;
+  size_t jseg_off = 0, jrej_off = 0, jdup_off = 0, outcome_off = 0;
+  size_t jdesc_off = 0, jclosed_off = 0, jinfo_off = 0;
+  size_t jstart_off = 0, ck_off = 0, iv_off = 0;
 };
-void lnext_layout(LNextLayout* L);
+// byte offsets into the device area of an indexed group: the IDs, the group-global segment ids
+// and the merged statuses the metadata launch reads, the reject bytes the check reads for the
+// outcome, and the metadata rows
+struct LNextJixDev {
+  size_t ids_off, gseg_off, mstatus_off, rej_off, ck_off, iv_off, bytes;
+};
+void lnext_jix_dev_layout(LNextJixDev* D);
+// what an indexed group adds to engine_lnext_issue
+struct LNextJixGroup {
+  prio3_engine* e = nullptr;  // nullptr: a plain group
+  uint32_t njix = 0, reps = 0, nseg = 0;
+};
+void lnext_layout(LNextLayout* L, bool jix = false);
+// group key: the field size, and one more bit for jobs that carry an index request
 uint32_t engine_lnext_key(const LNextJob* j);
 void engine_lnext_stage(LNextJob* j, uint8_t* stg, const LNextLayout& L);
 // launches the group's kernel on a pooled stream of `device` (reads and writes the staging)
 // n_acc aggregating jobs (descriptors 0 .. n_acc - 1 of the accumulate area; out_bytes its used
 // output bytes) are accumulated after the check, in an area the call takes from the scratch pool
 // (*slab_out, released after the stream by the finish)
+// jg (indexed groups): the index kernel runs first and the metadata launch last, over a second
+// area from the scratch pool (*slab2_out)
 int engine_lnext_issue(int device, uint32_t es, uint8_t* stg, uint8_t* stg_dev,
                        const LNextLayout& L, uint32_t n_jobs, uint32_t max_n, uint32_t n_acc,
-                       size_t out_bytes, hipStream_t* st_out, Slab** slab_out, bool own_queue);
+                       size_t out_bytes, hipStream_t* st_out, Slab** slab_out, bool own_queue,
+                       const LNextJixGroup* jg = nullptr, Slab** slab2_out = nullptr);
 size_t engine_lnext_out_bytes(const LNextJob* j);
 void engine_lnext_unstage(LNextJob* j, const uint8_t* stg, const LNextLayout& L);
+// folds the finished timing events of an indexed group's launches into its lead engine
+void engine_lnext_collect(prio3_engine* lead);
 int exec_leader_next(LNextJob* job);
 
 // ---- coalesced HPKE open of helper input shares (janus_hpke_open_input_shares) -----------

@@ -1334,18 +1334,26 @@ struct LNextPolicy {
     uint32_t jobs = 0, reps = 0, max_n = 0, es = 16;
     uint32_t acc_jobs = 0;  // aggregating jobs (next + accumulate)
     size_t out = 0;
+    // a group of jobs with an index request (every job of it is one: the key's extra bit)
+    prio3_engine* lead = nullptr;
+    uint32_t njix = 0, nseg = 0, nclosed = 0;
   };
   struct Handle {
     int device = 0;
     hipStream_t st = nullptr;
-    Slab* slab = nullptr;  // the accumulate area on the device (aggregating jobs)
+    Slab* slab = nullptr;   // the accumulate area on the device (aggregating jobs)
+    Slab* slab2 = nullptr;  // the index / metadata area on the device (indexed groups)
+    prio3_engine* lead = nullptr;
   };
   static uint64_t key(Job* j) { return engine_lnext_key(j); }
   static uint32_t reports(const State& s) { return s.reps; }
   static bool create(State& s, Job* j, size_t* bytes) {
     if (j->n > LNEXT_MAX_REPS || engine_lnext_out_bytes(j) > LNEXT_MAX_OUT) return false;
-    s.es = engine_lnext_key(j);
-    lnext_layout(&s.L);
+    if (j->jix && (j->nseg == 0 || j->nseg > EXEC_MAX_SEGS || j->nclosed > JIX_GROUP_CLOSED))
+      return false;
+    s.es = engine_lnext_key(j) & 0xffu;
+    s.lead = j->jix ? j->e : nullptr;
+    lnext_layout(&s.L, j->jix);
     *bytes = s.L.bytes;
     return true;
   }
@@ -1354,6 +1362,17 @@ struct LNextPolicy {
     if (s.jobs + 1 > LNEXT_MAX_JOBS || s.reps + j->n > LNEXT_MAX_REPS ||
         s.out + ob > LNEXT_MAX_OUT)
       return false;
+    if (j->jix) {
+      // a descriptor, the job's segments among the group's and its rows of the closed-interval
+      // table; a job that does not fit opens a new group
+      if (!s.L.jix || s.nseg + j->nseg > EXEC_MAX_SEGS || s.nclosed + j->nclosed > JIX_GROUP_CLOSED)
+        return false;
+      j->jslot = s.njix++;
+      j->seg0 = s.nseg;
+      j->closed0 = s.nclosed;
+      s.nseg += j->nseg;
+      s.nclosed += j->nclosed;
+    }
     j->slot = s.jobs++;
     j->rep_off = s.reps;
     s.reps += j->n;
@@ -1368,14 +1387,22 @@ struct LNextPolicy {
   static void stage(State& s, Staging& g, Job* j) { engine_lnext_stage(j, g.p, s.L); }
   static int issue(int device, State& s, Staging& g, Handle* h, bool own_queue) {
     h->device = device;
+    LNextJixGroup jg;
+    jg.e = s.njix ? s.lead : nullptr;
+    jg.njix = s.njix;
+    jg.reps = s.reps;
+    jg.nseg = s.nseg;
+    h->lead = jg.e;
     return engine_lnext_issue(device, s.es, g.p, g.dev, s.L, s.jobs, s.max_n, s.acc_jobs, s.out,
-                              &h->st, &h->slab, own_queue);
+                              &h->st, &h->slab, own_queue, &jg, &h->slab2);
   }
   static bool prepared(const Handle& h) { return done(h); }
   static bool done(const Handle& h) { return hipStreamQuery(h.st) != hipErrorNotReady; }
   static int finish(Handle* h) {
     const hipError_t q = hipStreamSynchronize(h->st);
     if (h->slab) ws_release(h->slab, h->st);
+    if (h->slab2) ws_release(h->slab2, h->st);
+    if (h->lead) engine_lnext_collect(h->lead);
     ws_exec_stream_put(h->device, h->st);
     return q == hipSuccess ? PRIO3_OK : PRIO3_EDEVICE;
   }
@@ -1531,7 +1558,7 @@ int exec_leader_next(LNextJob* job) {
   return g_lnext[job->device * EXEC_LANES].submit(job);
 }
 
-void lnext_layout(LNextLayout* L) {
+void lnext_layout(LNextLayout* L, bool jix) {
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   L->desc_off = 0;
   L->msg_off = up(sizeof(LNextDesc) * (size_t)LNEXT_MAX_JOBS);
@@ -1539,6 +1566,42 @@ void lnext_layout(LNextLayout* L) {
   L->acc_base = L->status_off + up((size_t)LNEXT_MAX_REPS);
   acc_layout(LNEXT_MAX_JOBS, LNEXT_MAX_REPS, LNEXT_MAX_OUT, &L->acc);
   L->bytes = L->acc_base + L->acc.bytes;
+  L->jix = jix;
+  if (!jix) return;
+  const size_t R = LNEXT_MAX_REPS, J = LNEXT_MAX_JOBS, S = EXEC_MAX_SEGS;
+  size_t off = L->bytes;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += up(bytes);
+    return at;
+  };
+  L->id_off = take(16 * R);
+  L->time_off = take(8 * R);
+  L->perr_off = take(R);
+  L->hacc_off = take(R);
+  L->jseg_off = take(4 * R);
+  L->jrej_off = take(R);
+  L->jdup_off = take(R);
+  L->outcome_off = take(R);
+  L->jdesc_off = take(sizeof(JixJobDesc) * J);
+  L->jclosed_off = take(16 * (size_t)JIX_GROUP_CLOSED);
+  L->jinfo_off = take(24 * J);
+  L->jstart_off = take(8 * S);
+  L->ck_off = take(32 * S);
+  L->iv_off = take(16 * S);
+  L->bytes = off;
+}
+
+void lnext_jix_dev_layout(LNextJixDev* D) {
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t R = LNEXT_MAX_REPS, S = EXEC_MAX_SEGS;
+  D->ids_off = 0;
+  D->gseg_off = D->ids_off + up(16 * R);
+  D->mstatus_off = D->gseg_off + up(4 * R);
+  D->rej_off = D->mstatus_off + up(R);
+  D->ck_off = D->rej_off + up(R);
+  D->iv_off = D->ck_off + up(32 * S);
+  D->bytes = D->iv_off + up(16 * S);
 }
 
 int exec_stats(int kind, int id, ExecStats* out) {

@@ -130,6 +130,22 @@ class Prio3HelperJobOut(C.Structure):
         "segment_ids", "segment_starts", "reject", "duplicate", "info", "prep_msgs", "status",
         "agg_shares", "counts", "checksums", "intervals")]
 
+class Prio3LeaderJobIn(C.Structure):
+    """prio3_leader_job_in (include/janus_prio3.h)."""
+    _fields_ = [("report_ids", C.c_void_p), ("times", C.c_void_p),
+                ("leader_status", C.c_void_p), ("prepare_error", C.c_void_p),
+                ("prep_msgs", C.c_void_p), ("time_precision", C.c_uint64),
+                ("closed_intervals", C.c_void_p), ("accept_mask", C.c_void_p),
+                ("k", C.c_uint32), ("max_segments", C.c_uint32)]
+
+
+class Prio3LeaderJobOut(C.Structure):
+    """prio3_leader_job_out (include/janus_prio3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "segment_ids", "segment_starts", "reject", "duplicate", "info", "status", "outcome",
+        "agg_shares", "counts", "checksums", "intervals")]
+
+
 #: Every symbol include/janus_prio3.h declares.
 EXPORTED_SYMBOLS = (
     "prio3_sizes", "prio3_engine_create", "prio3_engine_destroy", "prio3_helper_prepare_batch",
@@ -152,6 +168,7 @@ EXPORTED_SYMBOLS = (
     "prio3_selftest_field64",
     "prio3_device_leader_upload", "prio3_leader_upload_batch",
     "prio3_device_job_index", "prio3_job_index", "prio3_helper_aggregate_job",
+    "prio3_leader_finish_job",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -210,6 +227,7 @@ def load_library() -> C.CDLL:
                                                        vp, vp, vp, vp, vp, u32, vp, vp, vp, u32,
                                                        vp, vp, vp, vp]
     L.prio3_helper_aggregate_job.argtypes = [vp, P(Prio3HelperJobIn), P(Prio3HelperJobOut)]
+    L.prio3_leader_finish_job.argtypes = [vp, P(Prio3LeaderJobIn), P(Prio3LeaderJobOut)]
     L.prio3_debug_output_shares.argtypes = [vp, vp]
     L.prio3_batch_free.argtypes = [vp]
     L.prio3_batch_free.restype = None
@@ -450,6 +468,69 @@ class PreparedBatch:
         if rc:
             raise RuntimeError(f"prio3_leader_prepare_next_aggregate_batch failed (rc={rc})")
         return st, agg, cnt
+
+    def leader_finish_job(self, report_ids, times, leader_status, prep_msgs,
+                          time_precision: int, max_segments: int, prepare_error=None,
+                          closed_intervals=None, accept_mask=None) -> dict:
+        """The rest of a leader aggregation job in one call (prio3_leader_finish_job), once the
+        helper's response is decoded: the helper's ``prepare_error`` laid over the init
+        ``leader_status``, the job index (``job_index``), ``leader_prepare_next_aggregate`` over
+        the index's segment ids and its accept bytes ANDed with ``accept_mask``, the batch
+        metadata (``batch_metadata``) and the per-report outcome (``dap.leader_outcome``, then
+        BatchCollected for a report of a closed batch that had not failed), byte for byte what
+        those calls give.  Returns a dict: segment_ids [n], segment_starts [S], reject [n],
+        duplicate [n], the fields of Prio3JobIndexInfo, status [n], outcome [n], agg [S, agg_len],
+        counts [S], checksums [S, 32] and intervals [S, 2], with S = max_segments."""
+        sz, n = self.engine.sz, self.n
+        ids = np.ascontiguousarray(report_ids, np.uint8).reshape(-1, 16)
+        t = np.ascontiguousarray(times, np.uint64)
+        ls = np.ascontiguousarray(leader_status, np.uint8)
+        if ids.shape[0] != n or t.shape != (n,) or ls.shape != (n,):
+            raise ValueError("input shapes do not match the batch")
+        msgs = None
+        if sz.prep_msg_len:
+            msgs = np.ascontiguousarray(prep_msgs, np.uint8)
+            if msgs.shape != (n, sz.prep_msg_len):
+                raise ValueError("prepare message shape does not match the VDAF instance")
+        pe = m = None
+        if prepare_error is not None:
+            pe = np.ascontiguousarray(prepare_error, np.uint8)
+            if pe.shape != (n,):
+                raise ValueError("prepare_error must have one byte per report")
+        if accept_mask is not None:
+            m = np.ascontiguousarray(accept_mask, np.uint8)
+            if m.shape != (n,):
+                raise ValueError("accept_mask must have one byte per report")
+        cz, k = self.engine._closed(closed_intervals)
+        S = max(0, min(int(max_segments), 4096))
+        seg = np.zeros(n, np.uint32)
+        starts = np.zeros(S, np.uint64)
+        rej = np.zeros(n, np.uint8)
+        dup = np.zeros(n, np.uint8)
+        info = Prio3JobIndexInfo()
+        status = np.zeros(n, np.uint8)
+        outcome = np.zeros(n, np.uint8)
+        agg = np.zeros((S, sz.agg_share_len), np.uint8)
+        cnt = np.zeros(S, np.uint64)
+        ck = np.zeros((S, 32), np.uint8)
+        iv = np.zeros((S, 2), np.uint64)
+        a = lambda x: None if x is None else x.ctypes.data
+        jin = Prio3LeaderJobIn(
+            report_ids=a(ids), times=a(t), leader_status=a(ls), prepare_error=a(pe),
+            prep_msgs=a(msgs), time_precision=int(time_precision), closed_intervals=a(cz),
+            accept_mask=a(m), k=k, max_segments=int(max_segments))
+        jout = Prio3LeaderJobOut(
+            segment_ids=a(seg), segment_starts=a(starts), reject=a(rej), duplicate=a(dup),
+            info=C.addressof(info), status=a(status), outcome=a(outcome), agg_shares=a(agg),
+            counts=a(cnt), checksums=a(ck), intervals=a(iv))
+        rc = load_library().prio3_leader_finish_job(self.handle, C.byref(jin), C.byref(jout))
+        if rc:
+            raise RuntimeError(f"prio3_leader_finish_job failed (rc={rc})")
+        out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
+                   status=status, outcome=outcome, agg=agg, counts=cnt, checksums=ck,
+                   intervals=iv)
+        out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
+        return out
 
     def output_shares(self) -> np.ndarray:
         out = np.zeros((self.n, self.engine.sz.agg_share_len), np.uint8)
