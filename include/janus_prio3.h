@@ -555,6 +555,79 @@ int prio3_device_leader_prepare_next(prio3_engine* engine, uint32_t n, const uin
  * with n_segments == 1 finishes from them (the verdicts, the accept mask and out-of-range
  * segment ids are applied as corrections), any other accumulate reads the output shares. */
 
+/* ---- Ticketed job submission ---- */
+/* Every job call above parks its caller for the whole device round trip, so a process has no more
+ * jobs in flight than threads inside the library.  Each executor-backed job call has a submit
+ * form: the same arguments as its blocking twin, plus notify_fd and ticket_out.  Submit stages the
+ * job into its coalesced group on the calling thread and returns a ticket; prio3_ticket_wait
+ * later blocks until the job's group has run, writes the outputs and returns what the blocking
+ * call would have returned.  A thread may hold any number of tickets (Janus holds a rayon worker
+ * only for CPU work and awaits a oneshot, aggregator.rs:2100-2123,
+ * aggregation_job_driver.rs:449-462).
+ *  - Inputs are read only inside the submit call -- every input array, closed_intervals, the
+ *    accept mask, the task ID and the job structs themselves: the caller may reuse or free them as
+ *    soon as submit returns.
+ *  - Outputs are written only inside prio3_ticket_wait, on the waiting thread, and nothing is
+ *    written after it returns.  Two exceptions: out->status of prio3_leader_finish_job_submit is
+ *    in/out and is seeded (with leader_status) at submit; and the synchronous paths below write
+ *    during submit.  The output buffers (and *batch_out of the leader's prepare_init) must stay
+ *    valid until the wait.
+ *  - notify_fd (-1: none) is a caller-owned eventfd; several tickets may share one.  Once the
+ *    ticket's group is done -- with success or failure -- the library writes the 8-byte value 1 to
+ *    it: exactly once per ticket, never before prio3_ticket_poll would return 1, and never from
+ *    inside submit except on the synchronous paths.
+ *  - Synchronous paths.  A job its blocking twin does not run as one executor job -- an empty
+ *    job; one above PRIO3_JOB_GROUP_MAX_REPORTS / _MAX_SEGMENTS; an engine that cannot coalesce; a
+ *    job with more segments than one group holds; a leader engine that is not coalescable (FPVec,
+ *    the multiproof instance) -- runs that twin inside submit: the outputs are written there, the
+ *    ticket comes back done, notify_fd is written before submit returns, and the wait returns the
+ *    twin's result.  No size or instance is refused that the blocking form accepts;
+ *    PRIO3_FPVEC_BOUNDED_L2 stays PRIO3_EUNSUPPORTED under the same rule.
+ *  - Failure.  An argument error (or any failure before the job is queued) is the return value of
+ *    submit, with *ticket_out = NULL: nothing is outstanding and notify_fd is not written.  A
+ *    failure of the job's group is the return value of the wait.  A NULL ticket_out is
+ *    PRIO3_EINVAL.
+ *  - Ownership.  Every ticket must be waited exactly once, by one thread at a time; there is no
+ *    cancel.  A ticket that is done but not yet waited keeps its group's pinned staging (96 MB per
+ *    group) and counts as an active job of its executor until the wait.  Destroying an engine, an
+ *    opener or a prio3_batch with tickets pending on it is a caller error, as destroying one under
+ *    a blocked call is.
+ *  - Coalescing.  Tickets of one thread share groups with each other and with blocking callers.
+ *  - The calling thread's HIP device is left as it was, in submit and in wait. */
+typedef struct prio3_ticket prio3_ticket;
+int prio3_helper_prepare_aggregate_batch_submit(
+    prio3_engine* engine, uint32_t n, const uint8_t* nonces, const uint8_t* public_shares,
+    const uint8_t* helper_shares, const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
+    const uint8_t* accept_mask, uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out,
+    uint8_t* agg_shares_out, uint64_t* counts_out, int notify_fd, prio3_ticket** ticket_out);
+int prio3_helper_aggregate_init_batch_ex_submit(
+    prio3_engine* engine, struct janus_hpke_opener* opener,
+    struct janus_hpke_opener* fallback_opener, uint64_t report_deadline, uint32_t n,
+    const uint8_t task_id[32], int require_taskprov, const uint8_t* report_ids,
+    const uint64_t* times, const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct,
+    const uint32_t* ct_len, uint32_t ct_stride, const uint8_t* leader_prep_shares,
+    const uint32_t* segment_ids, const uint8_t* accept_mask, uint32_t n_segments,
+    uint8_t* prep_msgs_out, uint8_t* status_out, uint8_t* agg_shares_out, uint64_t* counts_out,
+    int notify_fd, prio3_ticket** ticket_out);
+int prio3_helper_aggregate_job_submit(prio3_engine* engine, const prio3_helper_job_in* job,
+                                      const prio3_helper_job_out* out, int notify_fd,
+                                      prio3_ticket** ticket_out);
+/* *batch_out (nullable pointer) is filled by the wait */
+int prio3_leader_prepare_init_batch_submit(prio3_engine* engine, uint32_t n, const uint8_t* nonces,
+                                           const uint8_t* public_shares,
+                                           const uint8_t* leader_input_shares,
+                                           uint8_t* prep_shares_out, uint8_t* status_out,
+                                           prio3_batch** batch_out, int notify_fd,
+                                           prio3_ticket** ticket_out);
+int prio3_leader_finish_job_submit(prio3_batch* batch, const prio3_leader_job_in* job,
+                                   const prio3_leader_job_out* out, int notify_fd,
+                                   prio3_ticket** ticket_out);
+/* 1: the ticket's job is done (prio3_ticket_wait will not block), 0: pending.  Never blocks. */
+int prio3_ticket_poll(const prio3_ticket* ticket);
+/* Blocks until the job is done, writes its outputs, frees the ticket and returns what the blocking
+ * call would have returned (PRIO3_EINVAL for a NULL ticket). */
+int prio3_ticket_wait(prio3_ticket* ticket);
+
 /* ---- Leader upload ---- */
 /* The leader's upload handler for a batch of one task (VdafOps::handle_upload_generic,
  * aggregator/src/aggregator.rs:1522-1702; Janus batches the stored reports in ReportWriteBatcher):

@@ -39,15 +39,13 @@ Pool& pool() {
   return *p;
 }
 
-// `threads` workers taking jobs 0..jobs-1 in order; returns elapsed seconds (< 0: a call failed)
-template <class F>
-double run_pool(int threads, int jobs, F job) {
+// `work` once on each of `threads` pool threads; returns elapsed seconds
+double run_threads(int threads, const std::function<void()>& work) {
   Pool& P = pool();
   // one caller at a time: the pool has one work slot, and a second caller arriving inside a run
   // would replace the work its threads are still picking up
   static std::mutex call_mu;
   std::lock_guard<std::mutex> call(call_mu);
-  std::atomic<int> next{0}, failed{0};
   std::unique_lock<std::mutex> lk(P.mu);
   while (P.threads < threads) {
     const int idx = P.threads++;
@@ -66,13 +64,7 @@ double run_pool(int threads, int jobs, F job) {
       }
     }).detach();
   }
-  P.work = [&] {
-    for (;;) {
-      const int j = next.fetch_add(1);
-      if (j >= jobs) return;
-      if (!job(j)) failed = 1;
-    }
-  };
+  P.work = work;
   P.want = threads;
   P.active = threads;
   P.gen++;
@@ -81,6 +73,54 @@ double run_pool(int threads, int jobs, F job) {
   P.done.wait(lk, [&] { return P.active == 0; });
   const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   P.work = nullptr;
+  return dt;
+}
+
+// `threads` workers taking jobs 0..jobs-1 in order; returns elapsed seconds (< 0: a call failed)
+template <class F>
+double run_pool(int threads, int jobs, F job) {
+  std::atomic<int> next{0}, failed{0};
+  const double dt = run_threads(threads, [&] {
+    for (;;) {
+      const int j = next.fetch_add(1);
+      if (j >= jobs) return;
+      if (!job(j)) failed = 1;
+    }
+  });
+  return failed ? -1.0 : dt;
+}
+
+// The same with tickets: each worker keeps up to K jobs outstanding -- it submits until it holds
+// K tickets, then waits the oldest and submits the next.  submit(j, slot, &ticket) starts job j
+// with the worker's output slot `slot` (0..K-1, free again once its ticket is waited).
+template <class F>
+double run_pool_tickets(int threads, int jobs, int K, F submit) {
+  std::atomic<int> next{0}, failed{0};
+  if (K < 1) K = 1;
+  const double dt = run_threads(threads, [&] {
+    std::vector<prio3_ticket*> ring((size_t)K, nullptr);
+    size_t head = 0, held = 0;  // the oldest ticket's slot, tickets held
+    auto wait_oldest = [&] {
+      if (prio3_ticket_wait(ring[head]) != PRIO3_OK) failed = 1;
+      ring[head] = nullptr;
+      head = (head + 1) % (size_t)K;
+      held--;
+    };
+    for (;;) {
+      const int j = next.fetch_add(1);
+      if (j >= jobs) break;
+      if (held == (size_t)K) wait_oldest();
+      const size_t slot = (head + held) % (size_t)K;
+      prio3_ticket* t = nullptr;
+      if (!submit(j, (int)slot, &t) || !t) {
+        failed = 1;
+        continue;
+      }
+      ring[slot] = t;
+      held++;
+    }
+    while (held) wait_oldest();
+  });
   return failed ? -1.0 : dt;
 }
 }  // namespace
@@ -130,6 +170,31 @@ double janus_jobs_run(prio3_engine** engines, int n_engines, const prio3_sizes_t
   });
 }
 
+// janus_jobs_run's combined form through prio3_helper_prepare_aggregate_batch_submit: every
+// worker keeps K tickets outstanding (K = 1: a blocking call in two halves).
+double janus_jobs_run_tickets(prio3_engine** engines, int n_engines, const prio3_sizes_t* szp,
+                              int threads, int jobs, int job_size, uint32_t pool,
+                              const uint8_t* nonces, const uint8_t* pub, const uint8_t* helper,
+                              const uint8_t* lps, uint8_t* status_out, uint64_t* counts_out,
+                              uint8_t* agg_out, int K) {
+  const prio3_sizes_t sz = *szp;
+  const uint32_t span = pool - (uint32_t)job_size + 1;
+  const size_t msg_bytes = (size_t)job_size * (sz.prep_msg_len ? sz.prep_msg_len : 1);
+  return run_pool_tickets(threads, jobs, K, [&](int j, int slot, prio3_ticket** tk) {
+    thread_local std::vector<uint8_t> msgs;  // one prepare-message buffer per outstanding ticket
+    msgs.resize(msg_bytes * (size_t)(K < 1 ? 1 : K));
+    const uint32_t t = (uint32_t)(j % n_engines);
+    const uint32_t r0 = t * pool + (uint32_t)(((uint64_t)(j / n_engines) * job_size) % span);
+    const uint8_t* jp = sz.public_share_len ? pub + (size_t)sz.public_share_len * r0 : nullptr;
+    counts_out[j] = 0;
+    return prio3_helper_prepare_aggregate_batch_submit(
+               engines[t], (uint32_t)job_size, nonces + 16 * (size_t)r0, jp,
+               helper + (size_t)sz.helper_share_len * r0, lps + (size_t)sz.prep_share_len * r0,
+               nullptr, nullptr, 1, msgs.data() + msg_bytes * (size_t)slot,
+               status_out + (size_t)j * job_size, agg_out + (size_t)sz.agg_share_len * j,
+               counts_out + j, -1, tk) == PRIO3_OK;
+  });
+}
 
 // The leader's side of the same jobs: per job prio3_leader_prepare_init_batch on the explicit
 // leader input shares lin[..][leader_input_share_len], prio3_leader_prepare_next_batch on the
@@ -349,6 +414,62 @@ double janus_jobs_run_job(prio3_engine** engines, int n_engines, const prio3_siz
                                 acc.data(), seg_out + o, max_segments, ck_out + 32 * S * j,
                                 iv_out + 2 * S * j);
     return rc == PRIO3_OK;
+  });
+}
+
+// janus_jobs_run_job's form 1 through prio3_helper_aggregate_job_submit: every worker keeps K
+// tickets outstanding.  Same inputs and outputs per job.
+double janus_jobs_run_job_tickets(prio3_engine** engines, int n_engines, const prio3_sizes_t* szp,
+                                  janus_hpke_opener* opener, const uint8_t* task_ids, int threads,
+                                  int jobs, int job_size, uint32_t pool, const uint8_t* nonces,
+                                  const uint8_t* pub, const uint64_t* times, const uint8_t* enc,
+                                  uint32_t nenc, const uint8_t* ct, const uint32_t* ct_len,
+                                  uint32_t ct_stride, const uint8_t* lps, uint64_t time_precision,
+                                  const uint64_t* closed, uint32_t k, uint32_t max_segments,
+                                  uint32_t* seg_out, uint64_t* starts_out, uint8_t* reject_out,
+                                  uint8_t* dup_out, prio3_job_index_info* info_out,
+                                  uint8_t* status_out, uint64_t* counts_out, uint8_t* agg_out,
+                                  uint8_t* ck_out, uint64_t* iv_out, int K) {
+  const prio3_sizes_t sz = *szp;
+  const uint32_t span = pool - (uint32_t)job_size + 1;
+  const size_t S = max_segments;
+  const size_t msg_bytes = (size_t)job_size * (sz.prep_msg_len ? sz.prep_msg_len : 1);
+  return run_pool_tickets(threads, jobs, K, [&](int j, int slot, prio3_ticket** tk) {
+    thread_local std::vector<uint8_t> msgs;  // one prepare-message buffer per outstanding ticket
+    msgs.resize(msg_bytes * (size_t)(K < 1 ? 1 : K));
+    const uint32_t t = (uint32_t)(j % n_engines);
+    const size_t r0 = t * (size_t)pool + (((uint64_t)(j / n_engines) * job_size) % span);
+    const size_t o = (size_t)j * job_size;
+    prio3_helper_job_in in{};
+    in.opener = opener;
+    in.report_deadline = UINT64_MAX;
+    in.n = (uint32_t)job_size;
+    in.task_id = task_ids + 32 * (size_t)t;
+    in.report_ids = nonces + 16 * r0;
+    in.times = times + r0;
+    in.public_shares = sz.public_share_len ? pub + (size_t)sz.public_share_len * r0 : nullptr;
+    in.enc = enc + (size_t)nenc * r0;
+    in.ct = ct + (size_t)ct_stride * r0;
+    in.ct_len = ct_len + r0;
+    in.leader_prep_shares = lps + (size_t)sz.prep_share_len * r0;
+    in.ct_stride = ct_stride;
+    in.k = k;
+    in.time_precision = time_precision;
+    in.closed_intervals = closed;
+    in.max_segments = max_segments;
+    prio3_helper_job_out out{};
+    out.segment_ids = seg_out + o;
+    out.segment_starts = starts_out + S * j;
+    out.reject = reject_out + o;
+    out.duplicate = dup_out + o;
+    out.info = info_out + j;
+    out.prep_msgs = msgs.data() + msg_bytes * (size_t)slot;
+    out.status = status_out + o;
+    out.agg_shares = agg_out + (size_t)sz.agg_share_len * S * j;
+    out.counts = counts_out + S * j;
+    out.checksums = ck_out + 32 * S * j;
+    out.intervals = iv_out + 2 * S * j;
+    return prio3_helper_aggregate_job_submit(engines[t], &in, &out, -1, tk) == PRIO3_OK;
   });
 }
 

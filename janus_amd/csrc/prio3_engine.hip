@@ -1884,6 +1884,101 @@ int prio3_device_output_shares(prio3_engine* e, uint32_t n, uint8_t* out) {
   return run_output_shares(R, 0, n, out, ps.s);
 }
 
+// ---- tickets (the *_submit entry points) ----
+// A job between its submit and its wait.  xt == nullptr: a synchronous path -- the blocking twin
+// ran inside submit and the ticket was born done.  Every entry point below has one body for both
+// forms: `tk` is nullptr for the blocking call, which then goes through the executor's blocking
+// submit exactly as before.
+struct prio3_ticket {
+  enum Kind { SYNC, HELPER, LEADER_INIT, LEADER_NEXT };
+  Kind kind = SYNC;
+  ExecTicket* xt = nullptr;
+  prio3_engine* e = nullptr;  // LEADER_INIT: the member the job was placed on, its report count
+  uint32_t n = 0;             // and where the batch handle goes
+  prio3_batch** batch_out = nullptr;
+};
+
+// the end of a synchronous path: the blocking form returns rc; the submit form hands out a done
+// ticket and writes the fd -- a failed call leaves nothing outstanding and the fd alone
+static int ticket_sync(int rc, int notify_fd, prio3_ticket** tk) {
+  if (!tk || rc != PRIO3_OK) return rc;
+  *tk = new prio3_ticket();
+  const uint64_t one = 1;
+  if (notify_fd >= 0) (void)!write(notify_fd, &one, sizeof one);
+  return PRIO3_OK;
+}
+
+static int ticket_queued(int rc, prio3_ticket::Kind kind, ExecTicket* xt, prio3_ticket** tk,
+                         prio3_engine* e = nullptr, uint32_t n = 0,
+                         prio3_batch** batch_out = nullptr) {
+  if (rc != PRIO3_OK) return rc;
+  prio3_ticket* t = new prio3_ticket();
+  t->kind = kind;
+  t->xt = xt;
+  t->e = e;
+  t->n = n;
+  t->batch_out = batch_out;
+  *tk = t;
+  return PRIO3_OK;
+}
+
+// a helper job of the prepare executor, blocking (tk == nullptr) or ticketed
+static int helper_exec(ExecJob* job, int notify_fd, prio3_ticket** tk) {
+  if (tk) {
+    ExecTicket* xt = nullptr;
+    return ticket_queued(exec_submit_begin(job, notify_fd, &xt), prio3_ticket::HELPER, xt, tk);
+  }
+  const int rc = exec_submit(job);
+  if (rc) return rc;
+  run_release(job->run, nullptr, false);  // no batch handle: the output shares are not kept
+  return PRIO3_OK;
+}
+
+static int leader_next_exec(LNextJob* job, int notify_fd, prio3_ticket** tk) {
+  if (!tk) return exec_leader_next(job);
+  ExecTicket* xt = nullptr;
+  return ticket_queued(exec_leader_next_begin(job, notify_fd, &xt), prio3_ticket::LEADER_NEXT, xt,
+                       tk);
+}
+
+int prio3_ticket_poll(const prio3_ticket* t) {
+  if (!t) return 1;
+  return !t->xt || exec_ticket_done(t->xt) ? 1 : 0;
+}
+
+int prio3_ticket_wait(prio3_ticket* t) {
+  if (!t) return PRIO3_EINVAL;
+  int rc = PRIO3_OK;
+  switch (t->kind) {
+    case prio3_ticket::SYNC: break;
+    case prio3_ticket::HELPER: {
+      TraceSpan span_("handle_aggregate_init_generic threadpool task");
+      ExecJob job;
+      rc = exec_ticket_complete(t->xt, &job);
+      if (rc == PRIO3_OK) run_release(job.run, nullptr, false);
+      break;
+    }
+    case prio3_ticket::LEADER_INIT: {
+      TraceSpan span_("leader VDAF preparation");
+      LeaderJob job{};
+      rc = exec_ticket_complete(t->xt, &job);
+      if (rc != PRIO3_OK) break;
+      if (t->batch_out)
+        *t->batch_out = new prio3_batch{t->e, job.run, job.c0, t->n};
+      else
+        run_release(job.run, nullptr, false);
+      break;
+    }
+    case prio3_ticket::LEADER_NEXT: {
+      TraceSpan span_("leader VDAF preparation");
+      rc = exec_ticket_complete(t->xt, nullptr);
+      break;
+    }
+  }
+  delete t;
+  return rc;
+}
+
 // ---- host-buffer entry points (what the Rust FFI calls from inside rayon::spawn) ----
 // A helper job of the prepare executor; nseg > 0: it also aggregates in the group's launch.  The
 // sealed form (helper_aggregate_init) adds its own fields.
@@ -1945,14 +2040,13 @@ int prio3_helper_prepare_batch(prio3_engine* e, uint32_t n, const uint8_t* nonce
                               prep_msgs_out, status_out, batch_out, false);
 }
 
-int prio3_helper_prepare_aggregate_batch(prio3_engine* e, uint32_t n, const uint8_t* nonces,
-                                         const uint8_t* public_shares,
-                                         const uint8_t* helper_shares,
-                                         const uint8_t* leader_prep_shares,
-                                         const uint32_t* segment_ids, const uint8_t* accept_mask,
-                                         uint32_t n_segments, uint8_t* prep_msgs_out,
-                                         uint8_t* status_out, uint8_t* agg_shares_out,
-                                         uint64_t* counts_out) {
+static int helper_prepare_aggregate(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                                    const uint8_t* public_shares, const uint8_t* helper_shares,
+                                    const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
+                                    const uint8_t* accept_mask, uint32_t n_segments,
+                                    uint8_t* prep_msgs_out, uint8_t* status_out,
+                                    uint8_t* agg_shares_out, uint64_t* counts_out, int notify_fd,
+                                    prio3_ticket** tk) {
   TraceSpan span_("handle_aggregate_init_generic threadpool task");
   if (!e || n_segments == 0 || !agg_shares_out || !counts_out ||
       (n && (!nonces || !helper_shares || !leader_prep_shares || !status_out)))
@@ -1976,15 +2070,37 @@ int prio3_helper_prepare_aggregate_batch(prio3_engine* e, uint32_t n, const uint
       memset(agg_shares_out, 0, agg_len * n_segments);
       memset(counts_out, 0, 8 * (size_t)n_segments);
     }
-    return rc;
+    return ticket_sync(rc, notify_fd, tk);
   }
   ExecJob job = helper_job(e, n, nonces, public_shares, helper_shares, leader_prep_shares,
                            prep_msgs_out, status_out, segment_ids, accept_mask, n_segments,
                            agg_shares_out, counts_out);
-  const int rc = exec_submit(&job);
-  if (rc) return rc;
-  run_release(job.run, nullptr, false);  // no batch handle: the output shares are not kept
-  return PRIO3_OK;
+  return helper_exec(&job, notify_fd, tk);
+}
+
+int prio3_helper_prepare_aggregate_batch(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                                         const uint8_t* public_shares,
+                                         const uint8_t* helper_shares,
+                                         const uint8_t* leader_prep_shares,
+                                         const uint32_t* segment_ids, const uint8_t* accept_mask,
+                                         uint32_t n_segments, uint8_t* prep_msgs_out,
+                                         uint8_t* status_out, uint8_t* agg_shares_out,
+                                         uint64_t* counts_out) {
+  return helper_prepare_aggregate(e, n, nonces, public_shares, helper_shares, leader_prep_shares,
+                                  segment_ids, accept_mask, n_segments, prep_msgs_out, status_out,
+                                  agg_shares_out, counts_out, -1, nullptr);
+}
+
+int prio3_helper_prepare_aggregate_batch_submit(
+    prio3_engine* e, uint32_t n, const uint8_t* nonces, const uint8_t* public_shares,
+    const uint8_t* helper_shares, const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
+    const uint8_t* accept_mask, uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out,
+    uint8_t* agg_shares_out, uint64_t* counts_out, int notify_fd, prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return helper_prepare_aggregate(e, n, nonces, public_shares, helper_shares, leader_prep_shares,
+                                  segment_ids, accept_mask, n_segments, prep_msgs_out, status_out,
+                                  agg_shares_out, counts_out, notify_fd, ticket_out);
 }
 
 // The two-call form of helper_aggregate_init for a job with more segments than one group can
@@ -2075,7 +2191,8 @@ static int helper_aggregate_init(
     const uint8_t* public_shares, const uint8_t* enc, const uint8_t* ct, const uint32_t* ct_len,
     uint32_t ct_stride, const uint8_t* leader_prep_shares, const uint32_t* segment_ids,
     const uint8_t* accept_mask, uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out,
-    uint8_t* agg_shares_out, uint64_t* counts_out) {
+    uint8_t* agg_shares_out, uint64_t* counts_out, int notify_fd = -1,
+    prio3_ticket** tk = nullptr) {
   TraceSpan span_("handle_aggregate_init_generic threadpool task");
   if (!e || !opener || !task_id || n_segments == 0 || !agg_shares_out || !counts_out ||
       ct_stride == 0 || ct_stride % 16 != 0 ||
@@ -2096,17 +2213,19 @@ static int helper_aggregate_init(
   if (n == 0) {
     memset(agg_shares_out, 0, agg_len * n_segments);
     memset(counts_out, 0, 8 * (size_t)n_segments);
-    return PRIO3_OK;
+    return ticket_sync(PRIO3_OK, notify_fd, tk);
   }
   e = place(e, n);
   IoLayout L1;
   engine_io_layout(e, 1, &L1);
   if (n_segments > L1.max_seg)
-    return aggregate_init_two_calls(e, opener, fallback_opener, report_deadline, n, task_id,
-                                    require_taskprov, report_ids, times, public_shares, enc, ct,
-                                    ct_len, ct_stride, leader_prep_shares, segment_ids,
-                                    accept_mask, n_segments, prep_msgs_out, status_out,
-                                    agg_shares_out, counts_out);
+    return ticket_sync(
+        aggregate_init_two_calls(e, opener, fallback_opener, report_deadline, n, task_id,
+                                 require_taskprov, report_ids, times, public_shares, enc, ct,
+                                 ct_len, ct_stride, leader_prep_shares, segment_ids, accept_mask,
+                                 n_segments, prep_msgs_out, status_out, agg_shares_out,
+                                 counts_out),
+        notify_fd, tk);
   // sealed input shares: no helper shares, the group opens them on the device
   ExecJob job = helper_job(e, n, report_ids, public_shares, nullptr, leader_prep_shares,
                            prep_msgs_out, status_out, segment_ids, accept_mask, n_segments,
@@ -2121,10 +2240,7 @@ static int helper_aggregate_init(
   job.require_taskprov = require_taskprov ? 1 : 0;
   job.fallback = fallback_opener;
   job.deadline = report_deadline;
-  const int rc = exec_submit(&job);
-  if (rc) return rc;
-  run_release(job.run, nullptr, false);
-  return PRIO3_OK;
+  return helper_exec(&job, notify_fd, tk);
 }
 
 // the plain form: no fallback keypair, no report deadline, public shares of 0 or 32 bytes
@@ -2155,6 +2271,23 @@ int prio3_helper_aggregate_init_batch_ex(
                                n_segments, prep_msgs_out, status_out, agg_shares_out, counts_out);
 }
 
+int prio3_helper_aggregate_init_batch_ex_submit(
+    prio3_engine* e, janus_hpke_opener* opener, janus_hpke_opener* fallback_opener,
+    uint64_t report_deadline, uint32_t n, const uint8_t task_id[32], int require_taskprov,
+    const uint8_t* report_ids, const uint64_t* times, const uint8_t* public_shares,
+    const uint8_t* enc, const uint8_t* ct, const uint32_t* ct_len, uint32_t ct_stride,
+    const uint8_t* leader_prep_shares, const uint32_t* segment_ids, const uint8_t* accept_mask,
+    uint32_t n_segments, uint8_t* prep_msgs_out, uint8_t* status_out, uint8_t* agg_shares_out,
+    uint64_t* counts_out, int notify_fd, prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return helper_aggregate_init(e, opener, fallback_opener, report_deadline, 64, n, task_id,
+                               require_taskprov, report_ids, times, public_shares, enc, ct,
+                               ct_len, ct_stride, leader_prep_shares, segment_ids, accept_mask,
+                               n_segments, prep_msgs_out, status_out, agg_shares_out, counts_out,
+                               notify_fd, ticket_out);
+}
+
 // The three calls prio3_helper_aggregate_job stands for, as a caller would make them: what a job
 // outside the in-group limits (and an empty one) runs, and what every other job's result equals.
 static int helper_job_three_calls(prio3_engine* e, const prio3_helper_job_in& in,
@@ -2178,8 +2311,9 @@ static int helper_job_three_calls(prio3_engine* e, const prio3_helper_job_in& in
                               out.segment_ids, S, out.checksums, out.intervals);
 }
 
-int prio3_helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
-                               const prio3_helper_job_out* out) {
+static int helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
+                                const prio3_helper_job_out* out, int notify_fd,
+                                prio3_ticket** tk) {
   TraceSpan span_("handle_aggregate_init_generic threadpool task");
   if (!e || !in || !out || !out->info) return PRIO3_EINVAL;
   const uint32_t n = in->n, S = in->max_segments;
@@ -2200,7 +2334,7 @@ int prio3_helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
   IoLayout L1;
   engine_io_layout(e, 1, &L1);
   if (n == 0 || n > JIX_GROUP_MAX_N || S > JIX_GROUP_MAX_SEG || S > L1.max_seg)
-    return helper_job_three_calls(e, *in, *out);
+    return ticket_sync(helper_job_three_calls(e, *in, *out), notify_fd, tk);
   e = place(e, n);
   ExecJob job = helper_job(e, n, in->report_ids, in->public_shares, nullptr,
                            in->leader_prep_shares, out->prep_msgs, out->status, nullptr,
@@ -2226,10 +2360,20 @@ int prio3_helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
   job.jinfo_out = out->info;
   job.ck_out = out->checksums;
   job.iv_out = out->intervals;
-  const int rc = exec_submit(&job);
-  if (rc) return rc;
-  run_release(job.run, nullptr, false);
-  return PRIO3_OK;
+  return helper_exec(&job, notify_fd, tk);
+}
+
+int prio3_helper_aggregate_job(prio3_engine* e, const prio3_helper_job_in* in,
+                               const prio3_helper_job_out* out) {
+  return helper_aggregate_job(e, in, out, -1, nullptr);
+}
+
+int prio3_helper_aggregate_job_submit(prio3_engine* e, const prio3_helper_job_in* in,
+                                      const prio3_helper_job_out* out, int notify_fd,
+                                      prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return helper_aggregate_job(e, in, out, notify_fd, ticket_out);
 }
 
 int prio3_accumulate(prio3_batch* b, const uint32_t* segment_ids, const uint8_t* accept_mask,
@@ -2418,10 +2562,15 @@ int prio3_device_leader_prepare_next(prio3_engine* e, uint32_t n, const uint8_t*
   return leader_next_launch(e, R, 0, n, d_prep_msgs, d_status, (hipStream_t)stream);
 }
 
-int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+static int leader_prepare_init_sync(prio3_engine* e, uint32_t n, const uint8_t* nonces,
                                     const uint8_t* public_shares,
                                     const uint8_t* leader_input_shares, uint8_t* prep_shares_out,
-                                    uint8_t* status_out, prio3_batch** batch_out) {
+                                    uint8_t* status_out, prio3_batch** batch_out);
+
+static int leader_prepare_init(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                               const uint8_t* public_shares, const uint8_t* leader_input_shares,
+                               uint8_t* prep_shares_out, uint8_t* status_out,
+                               prio3_batch** batch_out, int notify_fd, prio3_ticket** tk) {
   TraceSpan span_("leader VDAF preparation");
   if (e && fpvec_refused(e)) return PRIO3_EUNSUPPORTED;
   if (!e || (n && (!nonces || !leader_input_shares || !prep_shares_out || !status_out)))
@@ -2430,7 +2579,7 @@ int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* 
   if (n && d.jr_len && !public_shares) return PRIO3_EINVAL;
   if (n == 0) {
     if (batch_out) *batch_out = new prio3_batch{e, nullptr, 0, 0};
-    return PRIO3_OK;
+    return ticket_sync(PRIO3_OK, notify_fd, tk);
   }
   e = place(e, n);
   if (leader_coalescable(e)) {  // concurrent jobs (of any task of the instance): one launch
@@ -2442,6 +2591,11 @@ int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* 
     job.linput = leader_input_shares;
     job.prep_out = prep_shares_out;
     job.status_out = status_out;
+    if (tk) {  // the wait makes the batch handle
+      ExecTicket* xt = nullptr;
+      return ticket_queued(exec_leader_begin(&job, notify_fd, &xt), prio3_ticket::LEADER_INIT, xt,
+                           tk, e, n, batch_out);
+    }
     const int rc = exec_leader(&job);
     if (rc) return rc;
     if (batch_out)
@@ -2450,6 +2604,18 @@ int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* 
       run_release(job.run, nullptr, false);
     return PRIO3_OK;
   }
+  return ticket_sync(leader_prepare_init_sync(e, n, nonces, public_shares, leader_input_shares,
+                                              prep_shares_out, status_out, batch_out),
+                     notify_fd, tk);
+}
+
+// an engine whose leader jobs do not coalesce (FPVec, the multiproof instance, coalesce off): one
+// run per call (e: the member the job was placed on)
+static int leader_prepare_init_sync(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                                    const uint8_t* public_shares,
+                                    const uint8_t* leader_input_shares, uint8_t* prep_shares_out,
+                                    uint8_t* status_out, prio3_batch** batch_out) {
+  const DevParams& d = e->dp;
   DeviceGuard dg_(e->device);
   HIPCHK(dg_.rc);
   PooledStream ps(e->device);
@@ -2483,6 +2649,26 @@ int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* 
   else
     run_release(R, st, true);
   return PRIO3_OK;
+}
+
+int prio3_leader_prepare_init_batch(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                                    const uint8_t* public_shares,
+                                    const uint8_t* leader_input_shares, uint8_t* prep_shares_out,
+                                    uint8_t* status_out, prio3_batch** batch_out) {
+  return leader_prepare_init(e, n, nonces, public_shares, leader_input_shares, prep_shares_out,
+                             status_out, batch_out, -1, nullptr);
+}
+
+int prio3_leader_prepare_init_batch_submit(prio3_engine* e, uint32_t n, const uint8_t* nonces,
+                                           const uint8_t* public_shares,
+                                           const uint8_t* leader_input_shares,
+                                           uint8_t* prep_shares_out, uint8_t* status_out,
+                                           prio3_batch** batch_out, int notify_fd,
+                                           prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return leader_prepare_init(e, n, nonces, public_shares, leader_input_shares, prep_shares_out,
+                             status_out, batch_out, notify_fd, ticket_out);
 }
 
 int prio3_leader_prepare_next_batch(prio3_batch* b, const uint8_t* prep_msgs,
@@ -2607,8 +2793,8 @@ static int leader_job_composition(prio3_batch* b, const prio3_leader_job_in& in,
 // process_response_from_helper's per-report work and the writer's bookkeeping for one leader job
 // (aggregation_job_driver.rs:629-770, aggregation_job_writer.rs:540-695) in one trip through the
 // prepare_next executor: index, overlay + check, accumulate, metadata.
-int prio3_leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
-                            const prio3_leader_job_out* out) {
+static int leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
+                             const prio3_leader_job_out* out, int notify_fd, prio3_ticket** tk) {
   TraceSpan span_("leader VDAF preparation");
   if (!b || !in || !out || !out->info) return PRIO3_EINVAL;
   prio3_engine* e = b->e;
@@ -2629,7 +2815,7 @@ int prio3_leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
   const bool group = R && n && n <= JIX_GROUP_MAX_N && S <= JIX_GROUP_MAX_SEG &&
                      leader_coalescable(e) && R->msgs && R->linput &&
                      engine_lnext_out_bytes(&job) <= LNEXT_MAX_OUT;
-  if (!group) return leader_job_composition(b, *in, *out);
+  if (!group) return ticket_sync(leader_job_composition(b, *in, *out), notify_fd, tk);
   memcpy(out->status, in->leader_status, n);  // in/out: the overlay is the kernel's
   job.c0 = b->c0;
   job.n = n;
@@ -2654,7 +2840,20 @@ int prio3_leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
   job.outcome_out = out->outcome;
   job.ck_out = out->checksums;
   job.iv_out = out->intervals;
-  return exec_leader_next(&job);
+  return leader_next_exec(&job, notify_fd, tk);
+}
+
+int prio3_leader_finish_job(prio3_batch* b, const prio3_leader_job_in* in,
+                            const prio3_leader_job_out* out) {
+  return leader_finish_job(b, in, out, -1, nullptr);
+}
+
+int prio3_leader_finish_job_submit(prio3_batch* b, const prio3_leader_job_in* in,
+                                   const prio3_leader_job_out* out, int notify_fd,
+                                   prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return leader_finish_job(b, in, out, notify_fd, ticket_out);
 }
 
 int prio3_trace_enabled(void) { return trace_enabled() ? 1 : 0; }

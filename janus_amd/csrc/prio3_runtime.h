@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "prio3_exec.h"
+
 // ---- the calling thread's current device -------------------------------------------------
 // Every C entry point (and every runtime helper that needs a device current) makes its GPU
 // current through this guard and gives the calling thread its own device back on return: a Janus
@@ -172,11 +174,8 @@ struct ExecJob {
 // engines with the same VDAF instance on the same executor).
 int exec_submit(ExecJob* job);
 
-// Executor control and counters (prio3_executor_control / prio3_engine_members).
-struct ExecStats {
-  uint64_t jobs = 0, reports = 0, groups = 0;  // submitted jobs / their reports / launches
-  uint64_t active_jobs = 0, active_reports = 0;  // jobs inside submit now
-};
+// Executor control and counters (prio3_executor_control / prio3_engine_members): ExecStats of
+// prio3_exec.h.
 // kinds: 0 helper prepare, 1 accumulate, 2 leader prepare_init, 3 leader prepare_next,
 // 4 HPKE open of input shares
 enum { EXEC_PREP = 0, EXEC_ACC = 1, EXEC_LEADER = 2, EXEC_LNEXT = 3, EXEC_HPKE = 4, EXEC_KINDS = 5 };
@@ -504,6 +503,20 @@ void hpke_layout(const HpkeJob* j, uint32_t cap, HpkeLayout* L);
 int hpke_group_issue(const HpkeJob& proto, const HpkeLayout& L, const uint8_t* stg, uint8_t* out,
                      uint32_t n, hipStream_t* st_out, Slab** slab_out, bool own_queue);
 int exec_hpke(HpkeJob* job);
+
+// ---- tickets (the *_submit entry points of janus_prio3.h) ---------------------------------
+// The two halves of exec_submit / exec_leader / exec_leader_next (Exec::begin / done / complete of
+// prio3_exec.h).  begin copies *job, stages its inputs on the calling thread and returns; every
+// input the job points at has been read by then.  notify_fd (-1: none): an eventfd the executor
+// writes 1 to once the ticket's group is done.  complete blocks until then, writes the job's
+// outputs on the calling thread, copies the job with its results (run, c0) to job_out (the
+// kind's job struct; nullable) and frees the ticket.
+struct ExecTicket;
+int exec_submit_begin(const ExecJob* job, int notify_fd, ExecTicket** out);
+int exec_leader_begin(const LeaderJob* job, int notify_fd, ExecTicket** out);
+int exec_leader_next_begin(const LNextJob* job, int notify_fd, ExecTicket** out);
+bool exec_ticket_done(const ExecTicket* t);
+int exec_ticket_complete(ExecTicket* t, void* job_out);
 // the sealer's GPU and its KEM's Nenc (prio3_client_prepare_reports_device)
 struct janus_hpke_sealer;
 int hpke_sealer_device(const janus_hpke_sealer* s);

@@ -169,6 +169,9 @@ EXPORTED_SYMBOLS = (
     "prio3_device_leader_upload", "prio3_leader_upload_batch",
     "prio3_device_job_index", "prio3_job_index", "prio3_helper_aggregate_job",
     "prio3_leader_finish_job",
+    "prio3_helper_prepare_aggregate_batch_submit", "prio3_helper_aggregate_init_batch_ex_submit",
+    "prio3_helper_aggregate_job_submit", "prio3_leader_prepare_init_batch_submit",
+    "prio3_leader_finish_job_submit", "prio3_ticket_poll", "prio3_ticket_wait",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -228,6 +231,14 @@ def load_library() -> C.CDLL:
                                                        vp, vp, vp, vp]
     L.prio3_helper_aggregate_job.argtypes = [vp, P(Prio3HelperJobIn), P(Prio3HelperJobOut)]
     L.prio3_leader_finish_job.argtypes = [vp, P(Prio3LeaderJobIn), P(Prio3LeaderJobOut)]
+    # the ticketed twins: the same arguments, then notify_fd and ticket_out
+    for name in ("prio3_helper_prepare_aggregate_batch", "prio3_helper_aggregate_init_batch_ex",
+                 "prio3_helper_aggregate_job", "prio3_leader_finish_job"):
+        getattr(L, name + "_submit").argtypes = getattr(L, name).argtypes + [C.c_int, P(vp)]
+    L.prio3_leader_prepare_init_batch_submit.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, P(vp),
+                                                         C.c_int, P(vp)]
+    L.prio3_ticket_poll.argtypes = [vp]
+    L.prio3_ticket_wait.argtypes = [vp]
     L.prio3_debug_output_shares.argtypes = [vp, vp]
     L.prio3_batch_free.argtypes = [vp]
     L.prio3_batch_free.restype = None
@@ -416,6 +427,61 @@ def _seg_accept(n, segment_ids, accept_mask, n_segments):
     return seg, acc
 
 
+class Ticket:
+    """One submitted job (prio3_ticket*): ``poll()`` tells whether it is done without blocking,
+    ``wait()`` blocks until it is, and returns exactly what the blocking method returns.  The
+    ticket keeps every buffer the library was given alive until it has been waited: ``inputs``
+    (read by the library inside submit only) and ``outputs`` (written inside ``wait`` only, on the
+    waiting thread).  A ticket that is dropped without a wait is waited by ``__del__``: a done
+    ticket keeps its group's pinned staging (96 MB) until then."""
+
+    def __init__(self, name: str, handle: C.c_void_p, inputs: list, outputs: list, result):
+        self.name, self.handle = name, handle
+        self.inputs, self.outputs, self._result = inputs, outputs, result
+
+    def poll(self) -> bool:
+        if not self.handle:
+            return True
+        return bool(load_library().prio3_ticket_poll(self.handle))
+
+    def wait(self):
+        if not self.handle:
+            raise RuntimeError(f"{self.name}: the ticket has been waited already")
+        h, self.handle = self.handle, None
+        rc = load_library().prio3_ticket_wait(h)
+        result, self._result = self._result, None
+        self.inputs = []
+        if rc:
+            raise RuntimeError(f"{self.name} failed (rc={rc})")
+        return result()
+
+    def __del__(self):
+        try:
+            if self.handle:
+                h, self.handle = self.handle, None
+                load_library().prio3_ticket_wait(h)
+        except Exception:
+            pass
+
+
+def _job_call(name: str, args: tuple, inputs: list, outputs: list, result, ticket: bool,
+              notify_fd):
+    """The blocking call `name`, or (ticket) its ``_submit`` twin: `args` are the blocking form's,
+    `result` makes the method's return value from the output buffers once they are written."""
+    L = load_library()
+    if not ticket:
+        rc = getattr(L, name)(*args)
+        if rc:
+            raise RuntimeError(f"{name} failed (rc={rc})")
+        return result()
+    h = C.c_void_p()
+    rc = getattr(L, name + "_submit")(*args, -1 if notify_fd is None else int(notify_fd),
+                                      C.byref(h))
+    if rc:
+        raise RuntimeError(f"{name}_submit failed (rc={rc})")
+    return Ticket(name, h, [x for x in inputs if x is not None], outputs, result)
+
+
 class PreparedBatch:
     """Device-resident output shares of one ``prepare_batch`` call (prio3_batch*)."""
 
@@ -469,9 +535,21 @@ class PreparedBatch:
             raise RuntimeError(f"prio3_leader_prepare_next_aggregate_batch failed (rc={rc})")
         return st, agg, cnt
 
+    def submit_leader_finish_job(self, report_ids, times, leader_status, prep_msgs,
+                                 time_precision: int, max_segments: int, prepare_error=None,
+                                 closed_intervals=None, accept_mask=None,
+                                 notify_fd=None) -> Ticket:
+        """``leader_finish_job`` as a ticket (prio3_leader_finish_job_submit): the inputs are
+        consumed when this returns, ``wait()`` returns the blocking method's dict.  The batch must
+        outlive the ticket."""
+        return self.leader_finish_job(report_ids, times, leader_status, prep_msgs, time_precision,
+                                      max_segments, prepare_error, closed_intervals, accept_mask,
+                                      _ticket=True, _notify_fd=notify_fd)
+
     def leader_finish_job(self, report_ids, times, leader_status, prep_msgs,
                           time_precision: int, max_segments: int, prepare_error=None,
-                          closed_intervals=None, accept_mask=None) -> dict:
+                          closed_intervals=None, accept_mask=None, _ticket=False,
+                          _notify_fd=None) -> dict:
         """The rest of a leader aggregation job in one call (prio3_leader_finish_job), once the
         helper's response is decoded: the helper's ``prepare_error`` laid over the init
         ``leader_status``, the job index (``job_index``), ``leader_prepare_next_aggregate`` over
@@ -523,14 +601,18 @@ class PreparedBatch:
             segment_ids=a(seg), segment_starts=a(starts), reject=a(rej), duplicate=a(dup),
             info=C.addressof(info), status=a(status), outcome=a(outcome), agg_shares=a(agg),
             counts=a(cnt), checksums=a(ck), intervals=a(iv))
-        rc = load_library().prio3_leader_finish_job(self.handle, C.byref(jin), C.byref(jout))
-        if rc:
-            raise RuntimeError(f"prio3_leader_finish_job failed (rc={rc})")
-        out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
-                   status=status, outcome=outcome, agg=agg, counts=cnt, checksums=ck,
-                   intervals=iv)
-        out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
-        return out
+
+        def result():
+            out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
+                       status=status, outcome=outcome, agg=agg, counts=cnt, checksums=ck,
+                       intervals=iv)
+            out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
+            return out
+
+        return _job_call("prio3_leader_finish_job", (self.handle, C.byref(jin), C.byref(jout)),
+                         [self, ids, t, ls, pe, msgs, cz, m],
+                         [seg, starts, rej, dup, status, outcome, agg, cnt, ck, iv, info], result,
+                         _ticket, _notify_fd)
 
     def output_shares(self) -> np.ndarray:
         out = np.zeros((self.n, self.engine.sz.agg_share_len), np.uint8)
@@ -660,8 +742,17 @@ class HelperEngine:
             raise RuntimeError(f"prio3_helper_prepare_batch failed (rc={rc})")
         return msgs[:, :sz.prep_msg_len], status, PreparedBatch(self, bh, n)
 
+    def submit_prepare_aggregate_batch(self, nonces, public_shares, helper_shares,
+                                       leader_prep_shares, segment_ids=None, accept_mask=None,
+                                       n_segments: int = 1, notify_fd=None) -> Ticket:
+        """``prepare_aggregate_batch`` as a ticket (prio3_helper_prepare_aggregate_batch_submit)."""
+        return self.prepare_aggregate_batch(nonces, public_shares, helper_shares,
+                                            leader_prep_shares, segment_ids, accept_mask,
+                                            n_segments, _ticket=True, _notify_fd=notify_fd)
+
     def prepare_aggregate_batch(self, nonces, public_shares, helper_shares, leader_prep_shares,
-                                segment_ids=None, accept_mask=None, n_segments: int = 1):
+                                segment_ids=None, accept_mask=None, n_segments: int = 1,
+                                _ticket=False, _notify_fd=None):
         """prepare_batch + accumulate of the same reports in one coalesced launch
         (prio3_helper_prepare_aggregate_batch).  Returns (prep_msgs, status, agg [S, agg_len],
         counts [S])."""
@@ -683,18 +774,33 @@ class HelperEngine:
         status = np.zeros(n, np.uint8)
         agg = np.zeros((n_segments, sz.agg_share_len), np.uint8)
         cnt = np.zeros(n_segments, np.uint64)
-        rc = load_library().prio3_helper_prepare_aggregate_batch(
-            self.handle, n, _np_ptr(nonces), _np_ptr(pub), _np_ptr(helper_shares),
-            _np_ptr(leader_prep_shares), _np_ptr(seg), _np_ptr(acc), n_segments, _np_ptr(msgs),
-            _np_ptr(status), _np_ptr(agg), _np_ptr(cnt))
-        if rc:
-            raise RuntimeError(f"prio3_helper_prepare_aggregate_batch failed (rc={rc})")
-        return msgs[:, :sz.prep_msg_len], status, agg, cnt
+        return _job_call(
+            "prio3_helper_prepare_aggregate_batch",
+            (self.handle, n, _np_ptr(nonces), _np_ptr(pub), _np_ptr(helper_shares),
+             _np_ptr(leader_prep_shares), _np_ptr(seg), _np_ptr(acc), n_segments, _np_ptr(msgs),
+             _np_ptr(status), _np_ptr(agg), _np_ptr(cnt)),
+            [self, nonces, pub, helper_shares, leader_prep_shares, seg, acc],
+            [msgs, status, agg, cnt], lambda: (msgs[:, :sz.prep_msg_len], status, agg, cnt),
+            _ticket, _notify_fd)
+
+    def submit_aggregate_init_batch(self, opener, task_id: bytes, report_ids, times,
+                                    public_shares, enc, ct, ct_len, leader_prep_shares,
+                                    segment_ids=None, accept_mask=None, n_segments: int = 1,
+                                    require_taskprov=False, fallback_opener=None,
+                                    report_deadline=None, notify_fd=None) -> Ticket:
+        """``aggregate_init_batch`` as a ticket: always the _ex entry point
+        (prio3_helper_aggregate_init_batch_ex_submit; without a fallback keypair and a deadline it
+        is the plain call for every instance the plain call admits)."""
+        return self.aggregate_init_batch(opener, task_id, report_ids, times, public_shares, enc,
+                                         ct, ct_len, leader_prep_shares, segment_ids, accept_mask,
+                                         n_segments, require_taskprov, fallback_opener,
+                                         report_deadline, _ticket=True, _notify_fd=notify_fd)
 
     def aggregate_init_batch(self, opener, task_id: bytes, report_ids, times, public_shares,
                              enc, ct, ct_len, leader_prep_shares, segment_ids=None,
                              accept_mask=None, n_segments: int = 1, require_taskprov=False,
-                             fallback_opener=None, report_deadline=None):
+                             fallback_opener=None, report_deadline=None, _ticket=False,
+                             _notify_fd=None):
         """The helper's whole loop body for one job from the sealed input shares
         (prio3_helper_aggregate_init_batch; aggregator.rs:1794-2096): HPKE open with ``opener``
         (janus_amd.hpke.HpkeOpener), decode, prepare and accumulate in one coalesced launch.
@@ -731,17 +837,18 @@ class HelperEngine:
         agg = np.zeros((n_segments, sz.agg_share_len), np.uint8)
         cnt = np.zeros(n_segments, np.uint64)
         tid = (C.c_uint8 * 32).from_buffer_copy(task_id)
-        if fallback_opener is not None or report_deadline is not None:
+        if _ticket or fallback_opener is not None or report_deadline is not None:
             deadline = (1 << 64) - 1 if report_deadline is None else int(report_deadline)
-            rc = load_library().prio3_helper_aggregate_init_batch_ex(
-                self.handle, None if opener is None else opener.handle,
-                None if fallback_opener is None else fallback_opener.handle, deadline, n, tid,
-                int(bool(require_taskprov)), _np_ptr(ids), _np_ptr(t), _np_ptr(pub), _np_ptr(e),
-                _np_ptr(c), _np_ptr(cl), c.shape[1], _np_ptr(lps), _np_ptr(seg), _np_ptr(acc),
-                n_segments, _np_ptr(msgs), _np_ptr(status), _np_ptr(agg), _np_ptr(cnt))
-            if rc:
-                raise RuntimeError(f"prio3_helper_aggregate_init_batch_ex failed (rc={rc})")
-            return msgs[:, :sz.prep_msg_len], status, agg, cnt
+            return _job_call(
+                "prio3_helper_aggregate_init_batch_ex",
+                (self.handle, None if opener is None else opener.handle,
+                 None if fallback_opener is None else fallback_opener.handle, deadline, n, tid,
+                 int(bool(require_taskprov)), _np_ptr(ids), _np_ptr(t), _np_ptr(pub), _np_ptr(e),
+                 _np_ptr(c), _np_ptr(cl), c.shape[1], _np_ptr(lps), _np_ptr(seg), _np_ptr(acc),
+                 n_segments, _np_ptr(msgs), _np_ptr(status), _np_ptr(agg), _np_ptr(cnt)),
+                [self, opener, fallback_opener, tid, ids, t, pub, e, c, cl, lps, seg, acc],
+                [msgs, status, agg, cnt], lambda: (msgs[:, :sz.prep_msg_len], status, agg, cnt),
+                _ticket, _notify_fd)
         rc = load_library().prio3_helper_aggregate_init_batch(
             self.handle, opener.handle, n, tid, int(bool(require_taskprov)), _np_ptr(ids),
             _np_ptr(t), _np_ptr(pub), _np_ptr(e), _np_ptr(c), _np_ptr(cl), c.shape[1],
@@ -751,10 +858,23 @@ class HelperEngine:
             raise RuntimeError(f"prio3_helper_aggregate_init_batch failed (rc={rc})")
         return msgs[:, :sz.prep_msg_len], status, agg, cnt
 
+    def submit_aggregate_job(self, opener, task_id: bytes, report_ids, times, public_shares, enc,
+                             ct, ct_len, leader_prep_shares, time_precision: int,
+                             max_segments: int, closed_intervals=None, accept_mask=None,
+                             require_taskprov=False, fallback_opener=None, report_deadline=None,
+                             notify_fd=None) -> Ticket:
+        """``aggregate_job`` as a ticket (prio3_helper_aggregate_job_submit): the inputs are
+        consumed when this returns, ``wait()`` returns the blocking method's dict."""
+        return self.aggregate_job(opener, task_id, report_ids, times, public_shares, enc, ct,
+                                  ct_len, leader_prep_shares, time_precision, max_segments,
+                                  closed_intervals, accept_mask, require_taskprov, fallback_opener,
+                                  report_deadline, _ticket=True, _notify_fd=notify_fd)
+
     def aggregate_job(self, opener, task_id: bytes, report_ids, times, public_shares, enc, ct,
                       ct_len, leader_prep_shares, time_precision: int, max_segments: int,
                       closed_intervals=None, accept_mask=None, require_taskprov=False,
-                      fallback_opener=None, report_deadline=None) -> dict:
+                      fallback_opener=None, report_deadline=None, _ticket=False,
+                      _notify_fd=None) -> dict:
         """A whole helper aggregation job in one call (prio3_helper_aggregate_job): the job index
         (``job_index``), the loop body (``aggregate_init_batch`` with fallback keypair and report
         deadline) over the index's segment ids and its accept bytes ANDed with ``accept_mask``, and
@@ -813,17 +933,29 @@ class HelperEngine:
             segment_ids=a(seg), segment_starts=a(starts), reject=a(rej), duplicate=a(dup),
             info=C.addressof(info), prep_msgs=a(msgs), status=a(status), agg_shares=a(agg),
             counts=a(cnt), checksums=a(ck), intervals=a(iv))
-        rc = load_library().prio3_helper_aggregate_job(self.handle, C.byref(jin), C.byref(jout))
-        if rc:
-            raise RuntimeError(f"prio3_helper_aggregate_job failed (rc={rc})")
-        out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
-                   prep_msgs=msgs[:, :sz.prep_msg_len], status=status, agg=agg, counts=cnt,
-                   checksums=ck, intervals=iv)
-        out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
-        return out
+
+        def result():
+            out = dict(segment_ids=seg, segment_starts=starts, reject=rej, duplicate=dup,
+                       prep_msgs=msgs[:, :sz.prep_msg_len], status=status, agg=agg, counts=cnt,
+                       checksums=ck, intervals=iv)
+            out.update({f: int(getattr(info, f)) for f, _ in Prio3JobIndexInfo._fields_})
+            return out
+
+        return _job_call("prio3_helper_aggregate_job", (self.handle, C.byref(jin), C.byref(jout)),
+                         [self, opener, fallback_opener, tid, ids, t, pub, e, c, cl, lps, cz, m],
+                         [seg, starts, rej, dup, msgs, status, agg, cnt, ck, iv, info], result,
+                         _ticket, _notify_fd)
 
     # ---- leader side (same instance, agg_id 0) -----------------------------------
-    def leader_prepare_init_batch(self, nonces, public_shares, leader_input_shares):
+    def submit_leader_prepare_init_batch(self, nonces, public_shares, leader_input_shares,
+                                         notify_fd=None) -> Ticket:
+        """``leader_prepare_init_batch`` as a ticket (prio3_leader_prepare_init_batch_submit);
+        the batch handle is made by ``wait()``."""
+        return self.leader_prepare_init_batch(nonces, public_shares, leader_input_shares,
+                                              _ticket=True, _notify_fd=notify_fd)
+
+    def leader_prepare_init_batch(self, nonces, public_shares, leader_input_shares,
+                                  _ticket=False, _notify_fd=None):
         """Batched leader prepare_init (leader_initialized, aggregation_job_driver.rs:397-415).
 
         Returns (prep_shares [n, prep_share_len], status [n], batch); the batch's
@@ -842,12 +974,12 @@ class HelperEngine:
         ps = np.zeros((n, sz.prep_share_len), np.uint8)
         status = np.zeros(n, np.uint8)
         bh = C.c_void_p()
-        rc = load_library().prio3_leader_prepare_init_batch(
-            self.handle, n, _np_ptr(nonces), _np_ptr(pub), _np_ptr(ls), _np_ptr(ps),
-            _np_ptr(status), C.byref(bh))
-        if rc:
-            raise RuntimeError(f"prio3_leader_prepare_init_batch failed (rc={rc})")
-        return ps, status, PreparedBatch(self, bh, n)
+        return _job_call(
+            "prio3_leader_prepare_init_batch",
+            (self.handle, n, _np_ptr(nonces), _np_ptr(pub), _np_ptr(ls), _np_ptr(ps),
+             _np_ptr(status), C.byref(bh)),
+            [self, nonces, pub, ls], [ps, status, bh],
+            lambda: (ps, status, PreparedBatch(self, bh, n)), _ticket, _notify_fd)
 
     def leader_prepare_init_device(self, nonces, public_shares, leader_input_shares, prep_shares,
                                    status, stream=None) -> None:

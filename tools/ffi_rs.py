@@ -24,7 +24,8 @@ INTEGRATION = os.path.join(ROOT, "INTEGRATION.md")
 SCALARS = {"uint8_t": "u8", "uint16_t": "u16", "uint32_t": "u32", "uint64_t": "u64",
            "int8_t": "i8", "int16_t": "i16", "int32_t": "i32", "int64_t": "i64", "int": "c_int",
            "size_t": "usize", "char": "c_char", "double": "f64", "float": "f32", "void": "c_void"}
-OPAQUE = ("prio3_engine", "prio3_batch", "janus_hpke_opener", "janus_hpke_sealer")
+OPAQUE = ("prio3_engine", "prio3_batch", "prio3_ticket", "janus_hpke_opener",
+          "janus_hpke_sealer")
 
 
 def _strip_comments(src: str) -> str:
