@@ -222,7 +222,14 @@ int janus_hpke_selftest_p256(int op, uint32_t n, const uint32_t* a, const uint32
  * GF(2^521 - 1) (field 2, the P-521 KEM; 17 words) and GF(p384) (field 3, the P-384 KEM; 12
  * words, Montgomery form inside), operands canonical LE words below 2^448 / 2^521 / 2^384 --
  * op 0 a*b, 1 a^2, 2 a+b, 3 a-b, 4 a*39081 (X448) or 8a (P-521, P-384), 5 a^(p-2); results
- * canonical (fully reduced). */
+ * canonical (fully reduced).  Fields 1 and 2 also take chained ops, whose products see the limbs
+ * that add / sub / mul_small leave (k = 39081 for X448, 8 for P-521): 6 (a+b)(a-b), 7 (ka-b)^2,
+ * 8 E (AA + k E) with AA = (a+b)^2, BB = (a-b)^2, E = AA - BB, 9 x^2 with x = (a+a)+(b+b).
+ * Field 0 is GF(2^255 - 19) (the X25519 KEM; 8 words): operands raw and loosely reduced in
+ * [0, 2^256), no conversion, results the raw eight words -- op 0 a*b, 1 a^2, 2 a+b, 3 a-b,
+ * 4 121665 a, 5 a^(p-2) (all loosely reduced), 6 freeze(a) (canonical), 7 one Montgomery ladder
+ * step as in x25519_ladder's loop from x2 = a, z2 = b, x3 = b, z3 = a, x1 = a, returning
+ * freeze(x2' z3' + x3' z2'). */
 int janus_hpke_selftest_field(int field, int op, uint32_t n, const uint32_t* a, const uint32_t* b,
                               uint32_t* out);
 

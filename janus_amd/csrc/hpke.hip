@@ -1296,8 +1296,12 @@ __global__ __launch_bounds__(256) void k_selftest_p256(int op, uint32_t n, const
   for (int k = 0; k < 8; k++) out[8 * (size_t)i + k] = r.v[k];
 }
 
-// Test-only (janus_hpke_selftest_field): one operation of the X448 (field 1) or P-521 (field 2)
-// field code per element; operands and results as canonical little-endian 32-bit words (14 / 17)
+// Test-only (janus_hpke_selftest_field): one operation of the GF(2^255 - 19) (field 0), X448
+// (field 1), P-521 (field 2) or P-384 (field 3) field code per element.  Field 0: operands and
+// results are the raw eight limbs, loosely reduced in [0, 2^256), unconverted.  Fields 1 / 2:
+// operands and results as canonical little-endian 32-bit words (14 / 17); their ops 6..9 chain
+// add / sub / mul_small into a product, so the product sees the limbs it sees in the ladder and
+// in the Jacobian formulas (limbs 0 and 8, or limb 0, above their nominal width).
 __device__ p521::fp p521_from_words(const uint32_t* w) {
   p521::fp r;
 #pragma unroll
@@ -1325,7 +1329,37 @@ __global__ __launch_bounds__(256) void k_selftest_field(int field, int op, uint3
                                                         uint32_t* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (field == 1) {
+  if (field == 0) {
+    fe x, y, r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) x.v[k] = a[8 * (size_t)i + k], y.v[k] = b[8 * (size_t)i + k];
+    switch (op) {
+      case 0: r = fe_mul(x, y); break;
+      case 1: r = fe_sqr(x); break;
+      case 2: r = fe_add(x, y); break;
+      case 3: r = fe_sub(x, y); break;
+      case 4: r = fe_mul121665(x); break;
+      case 5: r = fe_inv(x); break;
+      case 6: r = fe_freeze(x); break;
+      default: {  // x25519_ladder's loop body, once, from (x2, z2, x3, z3) = (a, b, b, a), x1 = a
+        const fe x1 = x;
+        fe x2 = x, z2 = y, x3 = y, z3 = x;
+        const fe A = fe_add(x2, z2), B = fe_sub(x2, z2);
+        const fe AA = fe_sqr(A), BB = fe_sqr(B);
+        const fe E = fe_sub(AA, BB);
+        const fe C = fe_add(x3, z3), D = fe_sub(x3, z3);
+        const fe DA = fe_mul(D, A), CB = fe_mul(C, B);
+        x3 = fe_sqr(fe_add(DA, CB));
+        z3 = fe_mul(x1, fe_sqr(fe_sub(DA, CB)));
+        x2 = fe_mul(AA, BB);
+        z2 = fe_mul(E, fe_add(AA, fe_mul121665(E)));
+        r = fe_freeze(fe_add(fe_mul(x2, z3), fe_mul(x3, z2)));
+        break;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[8 * (size_t)i + k] = r.v[k];
+  } else if (field == 1) {
     uint32_t wa[14], wb[14], wr[14];
 #pragma unroll
     for (int k = 0; k < 14; k++) wa[k] = a[14 * (size_t)i + k], wb[k] = b[14 * (size_t)i + k];
@@ -1337,7 +1371,20 @@ __global__ __launch_bounds__(256) void k_selftest_field(int field, int op, uint3
       case 2: r = x448::add(x, y); break;
       case 3: r = x448::sub(x, y); break;
       case 4: r = x448::mul_small(x, 39081); break;
-      default: r = x448::inv(x); break;
+      case 5: r = x448::inv(x); break;
+      case 6: r = x448::mul(x448::add(x, y), x448::sub(x, y)); break;
+      case 7: r = x448::sqr(x448::sub(x448::mul_small(x, 39081), y)); break;
+      case 8: {
+        const auto AA = x448::sqr(x448::add(x, y)), BB = x448::sqr(x448::sub(x, y));
+        const auto E = x448::sub(AA, BB);
+        r = x448::mul(E, x448::add(AA, x448::mul_small(E, 39081)));
+        break;
+      }
+      default: {
+        const auto t = x448::add(x448::add(x, x), x448::add(y, y));
+        r = x448::mul(t, t);
+        break;
+      }
     }
     x448::to_words(r, wr);
 #pragma unroll
@@ -1374,7 +1421,20 @@ __global__ __launch_bounds__(256) void k_selftest_field(int field, int op, uint3
       case 2: r = p521::add(x, y); break;
       case 3: r = p521::sub(x, y); break;
       case 4: r = p521::mul_small(x, 8); break;
-      default: r = p521::inv(x); break;
+      case 5: r = p521::inv(x); break;
+      case 6: r = p521::mul(p521::add(x, y), p521::sub(x, y)); break;
+      case 7: r = p521::sqr(p521::sub(p521::mul_small(x, 8), y)); break;
+      case 8: {
+        const auto AA = p521::sqr(p521::add(x, y)), BB = p521::sqr(p521::sub(x, y));
+        const auto E = p521::sub(AA, BB);
+        r = p521::mul(E, p521::add(AA, p521::mul_small(E, 8)));
+        break;
+      }
+      default: {
+        const auto t = p521::add(p521::add(x, x), p521::add(y, y));
+        r = p521::mul(t, t);
+        break;
+      }
     }
     p521_to_words(r, wr);
 #pragma unroll
@@ -1386,9 +1446,10 @@ extern "C" {
 
 int janus_hpke_selftest_field(int field, int op, uint32_t n, const uint32_t* a, const uint32_t* b,
                               uint32_t* out) {
-  if (field < 1 || field > 3 || op < 0 || op > 5) return JANUS_HPKE_EINVAL;
+  if (field < 0 || field > 3 || op < 0 || op > (field == 0 ? 7 : field == 3 ? 5 : 9))
+    return JANUS_HPKE_EINVAL;
   if (n == 0) return JANUS_HPKE_OK;
-  const size_t m = (size_t)n * (field == 1 ? 14 : field == 3 ? 12 : 17) * 4;
+  const size_t m = (size_t)n * (field == 0 ? 8 : field == 1 ? 14 : field == 3 ? 12 : 17) * 4;
   void *da = nullptr, *db = nullptr, *dout = nullptr;
   int rc = JANUS_HPKE_OK;
   if (hipMalloc(&da, m) != hipSuccess || hipMalloc(&db, m) != hipSuccess ||

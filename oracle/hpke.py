@@ -57,6 +57,8 @@ def lib():
         _lib.hpke_kem_public.argtypes = [u16, vp, vp]
         _lib.hpke_open_suite.argtypes = [u16, u16, u16] + _lib.hpke_open.argtypes
         _lib.hpke_seal_suite.argtypes = [u16, u16, u16] + _lib.hpke_seal.argtypes
+        _lib.hpke_seal_to_enc_suite.argtypes = [u16, u16, u16, vp, vp, vp, vp, C.c_size_t, vp,
+                                                C.c_size_t, vp, C.c_size_t, vp]
         _lib.hpke_open_input_shares_suite.argtypes = [u16, u16, u16] + \
             _lib.hpke_open_input_shares.argtypes
         _lib.hpke_make_input_shares_suite.argtypes = [u16, u16, u16] + \
@@ -120,6 +122,17 @@ def seal(pkR: bytes, skE: bytes, info: bytes, aad: bytes, pt: bytes, aead=1, kem
     assert lib().hpke_seal_suite(kem, kdf, aead, _p(pkR), _p(skE), _p(info), len(info), _p(aad),
                                  len(aad), _p(pt), len(pt), enc, ct) == 0
     return enc.raw, ct.raw
+
+
+def seal_to_enc(skR: bytes, pkR: bytes, enc: bytes, info: bytes, aad: bytes, pt: bytes, aead=1,
+                kem=KEM_X25519, kdf=KDF_SHA256):
+    """Recipient-side seal: the ciphertext that opens under the chosen `enc` (an edge point whose
+    ephemeral private key nobody knows), or None where Decap refuses enc."""
+    assert len(enc) == nenc(kem)
+    ct = C.create_string_buffer(len(pt) + 16)
+    rc = lib().hpke_seal_to_enc_suite(kem, kdf, aead, _p(skR), _p(pkR), _p(enc), _p(info),
+                                      len(info), _p(aad), len(aad), _p(pt), len(pt), ct)
+    return None if rc else ct.raw
 
 
 def input_share_aad(task_id: bytes, report_id: bytes, time: int, public_share: bytes) -> bytes:

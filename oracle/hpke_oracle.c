@@ -284,6 +284,19 @@ int hpke_seal_suite(uint16_t kem, uint16_t kdf, uint16_t aead, const uint8_t* pk
   key_schedule(kem, kdf, aead, ss, kdf_nh(K->kdf), info, infolen, key, nonce);
   return aead_crypt(aead, 0, key, nonce, aad, aadlen, pt, ptlen, ct, ct + ptlen);
 }
+/* recipient-side seal: the ciphertext a sender whose Encap gave `enc` would have produced, built
+ * from the recipient's Decap (nobody knows the ephemeral private key of a chosen enc, such as a
+ * low-order or non-canonical point).  Writes ct[ptlen + 16]; -1 where Decap refuses enc. */
+int hpke_seal_to_enc_suite(uint16_t kem, uint16_t kdf, uint16_t aead, const uint8_t* skR,
+                           const uint8_t* pkR, const uint8_t* enc, const uint8_t* info,
+                           size_t infolen, const uint8_t* aad, size_t aadlen, const uint8_t* pt,
+                           size_t ptlen, uint8_t* ct) {
+  uint8_t ss[64], key[32], nonce[12];
+  const Kem* K = kem_of(kem);
+  if (!K || !kdf_md(kdf) || decap(K, enc, skR, pkR, ss)) return -1;
+  key_schedule(kem, kdf, aead, ss, kdf_nh(K->kdf), info, infolen, key, nonce);
+  return aead_crypt(aead, 0, key, nonce, aad, aadlen, pt, ptlen, ct, ct + ptlen);
+}
 int hpke_seal_kem(uint16_t kem, uint16_t aead, const uint8_t* pkR, const uint8_t skE[32],
                   const uint8_t* info, size_t infolen, const uint8_t* aad, size_t aadlen,
                   const uint8_t* pt, size_t ptlen, uint8_t* enc, uint8_t* ct) {

@@ -261,6 +261,54 @@ def test_recipient_key_edges():
         assert (st == G.SEAL_KEY_ERROR).all() and cts == [None] * n
 
 
+def _u32le(u):
+    return u.to_bytes(32, "little")
+
+
+def test_x25519_recipient_key_edges_accepted():
+    """A recipient key that is a non-canonical u (p + k up to 2^255 - 1), has bit 255 set, or is
+    an ordinary small point: the device masks bit 255 and reduces as RFC 7748 says, so both
+    forms give the oracle's bytes (kem_context carries pkR as given)."""
+    from janus_amd import hpke as G
+    from tests.test_hpke_edges import X25519_ACCEPTED
+    kem = H.KEM_X25519
+    n = 5
+    rng = np.random.default_rng(12)
+    sks = [H.kem_private(rng, kem) for _ in range(n)]
+    pts, aads = _messages(n, 8)
+    for u in X25519_ACCEPTED:
+        pkR = _u32le(u)
+        exp = _expect(pkR, sks, pts, aads, kem)
+        s = G.HpkeSealer(pkR, INFO, kem_id=kem)
+        _check_rows(exp, *_seal_device(s, sks, pts, aads))
+        enc, cts, st = s.seal(sks, pts, aads)
+        assert not st.any(), hex(u)
+        for i, (e, c) in enumerate(exp):
+            assert enc[i].tobytes() == e and cts[i] == c, (hex(u), i)
+        s.close()
+
+
+def test_x25519_recipient_key_edges_refused():
+    """Each of the seven low-order u, with bit 255 clear and set, gives an all-zero shared
+    secret: SEAL_KEY_ERROR for every row, zero rows and ct_len 0, in both forms."""
+    from janus_amd import hpke as G
+    from tests.test_hpke_edges import X25519_REFUSED
+    kem = H.KEM_X25519
+    n = 5
+    rng = np.random.default_rng(13)
+    sks = [H.kem_private(rng, kem) for _ in range(n)]
+    pts, aads = _messages(n, 9)
+    assert len(X25519_REFUSED) == 14
+    for u in X25519_REFUSED:
+        s = G.HpkeSealer(_u32le(u), INFO, kem_id=kem)
+        enc, ct, cl, st = _seal_device(s, sks, pts, aads)
+        assert (st == G.SEAL_KEY_ERROR).all(), hex(u)
+        assert not cl.any() and not enc.any() and not ct.any(), hex(u)
+        enc, cts, st = s.seal(sks, pts, aads)
+        assert (st == G.SEAL_KEY_ERROR).all() and cts == [None] * n and not enc.any(), hex(u)
+        s.close()
+
+
 def test_create_errors():
     from janus_amd import hpke as G
     L = G._lib()

@@ -375,8 +375,9 @@ def test_gpu_p256_field_ops_match_python(op):
     n = 4096 if op == 6 else 1 << 16
     a = [rnd.choice(P256_EDGE) if rnd.random() < 0.2 else rnd.randrange(2**256) for _ in range(n)]
     b = [rnd.choice(P256_EDGE) if rnd.random() < 0.2 else rnd.randrange(2**256) for _ in range(n)]
-    a[:len(P256_EDGE)] = P256_EDGE
-    b[:len(P256_EDGE)] = P256_EDGE[::-1]
+    k = len(P256_EDGE)  # the full edge x edge cross product first, random operands after it
+    a[:k * k] = [x for x in P256_EDGE for _ in P256_EDGE]
+    b[:k * k] = [y for _ in P256_EDGE for y in P256_EDGE]
     enc = lambda xs: np.frombuffer(b"".join(x.to_bytes(32, "little") for x in xs), np.uint32).copy()
     A, B = enc(a), enc(b)
     out = np.zeros_like(A)
@@ -483,8 +484,9 @@ def test_gpu_x448_p521_field_ops_match_python(field, op):
     n = 2048 if op == 5 else 1 << 15
     a = [rnd.choice(edge) if rnd.random() < 0.2 else rnd.randrange(2**bits) for _ in range(n)]
     bb = [rnd.choice(edge) if rnd.random() < 0.2 else rnd.randrange(2**bits) for _ in range(n)]
-    a[:len(edge)] = edge
-    bb[:len(edge)] = edge[::-1]
+    k = len(edge)  # the full edge x edge cross product first, random operands after it
+    a[:k * k] = [x for x in edge for _ in edge]
+    bb[:k * k] = [y for _ in edge for y in edge]
     enc = lambda xs: np.frombuffer(b"".join(x.to_bytes(4 * nw, "little") for x in xs),
                                    np.uint32).copy()
     A, B = enc(a), enc(bb)
