@@ -603,6 +603,11 @@ struct Mp64Params {
 };
 
 struct prio3_engine;
+// Whole 168-byte rate blocks in the joint-rand part's input ahead of the last: the 42-byte prefix
+// and a Field128 measurement share of meas_len elements.  The dual-state XOF kernels (k_xofd,
+// k_prep_h, k_prep_sum, the lane-pair kernels) need at least two; their share loops run B - 1 times.
+constexpr uint32_t jr_share_blocks(uint32_t meas_len) { return (42 + meas_len * 16) / 168; }
+constexpr bool share_spans_two_blocks(uint32_t meas_len) { return jr_share_blocks(meas_len) >= 2; }
 // prio3_query_sum.hip: true if launched (Prio3Sum with 16 <= P <= 128)
 bool query_sum_takes(const DevParams& p);
 bool launch_query_sum(const DevParams& p, InPtrs in, Scratch sc, OutPtrs out, hipStream_t st,

@@ -466,7 +466,9 @@ static size_t run_carve(Run* R, unsigned flags, uint8_t* base) {
     take(&R->sc.acc, fp ? 16 : es * d.arity * ld);
     take(&R->sc.out, own_out(d) ? es * d.out_len * ldo : 16);
     take(&R->sc.beta, es * d.calls * ld);
-    if (es == 16 && d.P == 32) take(&R->redo_list, 4 * n);  // (the k_prep_h instances)
+    // k_prep_h's list of flagged reports.  Wider than the plan's redo_list (any Field128 instance
+    // with P = 32, whatever the options and the run's size): slab sizes feed the pool budget.
+    if (es == 16 && d.P == 32) take(&R->redo_list, 4 * n);
     // FPVec runs in sub-batches of ld columns: the leader's corrected seeds of every report
     // outlive their sub-batch's scratch (prepare_next reads them)
     if (fp) take(&R->corr_all, 16 * n);
@@ -610,7 +612,7 @@ static uint64_t fnv(uint64_t h, const void* p, size_t n) {
 
 // aggregating jobs start at a wave boundary where the XOF fuses the accumulate (their waves then
 // hold one job's reports and fuse; the pad columns carry an out-of-range segment id)
-uint32_t engine_job_align(const prio3_engine* e) { return fusable(e) ? 64u : 1u; }
+uint32_t engine_job_align(const prio3_engine* e) { return prepare_fuses(e) ? 64u : 1u; }
 
 uint64_t engine_group_key(const prio3_engine* e) {
   uint64_t h = 1469598103934665603ull;
@@ -832,7 +834,7 @@ int engine_group_issue(prio3_engine* lead, const GroupView& g, GroupRun* gr, boo
   // wave partials of the XOF where the instance fuses; waves that straddle two jobs and the
   // excluded reports go through the fix-up list)
   const bool agg = g.nseg > 0;
-  const bool fuse = agg && fusable(lead);
+  const bool fuse = agg && prepare_fuses(lead);
   IoLayout L;
   if (g.L)
     L = *g.L;
@@ -1127,7 +1129,7 @@ void engine_leader_layout(const prio3_engine* e, uint32_t cap, LeaderLayout* L) 
     const char* v = getenv("JANUS_LEADER_SOA");
     return v && atoi(v) != 0;
   }();
-  L->lin_soa = leader_prep_takes(e) && soa;
+  L->lin_soa = plan_leader(e).soa_staging && soa;
 }
 
 // A leader group: the explicit input shares (5.6 KB per Histogram(256) report) go to the run by
@@ -1724,7 +1726,7 @@ int prio3_device_prepare_aggregate(prio3_engine* e, uint32_t n, const uint8_t* d
   DeviceGuard dg_(e->device);
   HIPCHK(dg_.rc);
   hipStream_t st = (hipStream_t)stream;  // NULL = the null stream (HIP convention)
-  const bool fuse = n > 0 && fusable(e);
+  const bool fuse = n > 0 && prepare_fuses(e);
   int rc = PRIO3_OK;
   Run* R = device_run(e, n, RUN_SCRATCH | (fuse ? (unsigned)RUN_FUSED : 0u), n_segments, st, &rc);
   if (!R) return rc;
@@ -2538,7 +2540,7 @@ int prio3_device_leader_prepare_init(prio3_engine* e, uint32_t n, const uint8_t*
   HIPCHK(dg_.rc);
   hipStream_t st = (hipStream_t)stream;
   int rc = PRIO3_OK;
-  const bool lfuse = leader_fuse_takes(e);
+  const bool lfuse = plan_leader(e).fuse_acc;
   Run* R = device_run(e, n, RUN_SCRATCH | (lfuse ? (unsigned)RUN_FUSED : 0u), lfuse ? 1u : 0u, st,
                       &rc);
   if (!R) return rc;

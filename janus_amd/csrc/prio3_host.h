@@ -136,9 +136,49 @@ struct PullRanges {
 bool launch_pull(const PullRanges& pr, unsigned blocks, hipStream_t st);
 
 // ---- prio3_prepare.hip (described at their definitions) ----
-bool fusable(const prio3_engine* e);
-bool leader_fuse_takes(const prio3_engine* e);
-bool leader_prep_takes(const prio3_engine* e);
+// What one helper prepare of n reports launches: decided once, in plan_prepare, and only read by
+// prepare_run, launch_prepare and launch_slow_redo (tests/golden/launch_table.json pins it).
+enum class PrepChain : uint8_t {
+  MP64,       // k_mp64_prepare
+  FPVEC,      // sub-batches of XOF, k_xof_slow and the FPVec query
+  FUSED_H,    // k_prep_h (or k_prep_hp on lane pairs): XOF + k_query_h<2, 32> in one launch
+  FUSED_SUM,  // k_prep_sum: XOF + k_query_sum in one launch
+  XOF_QUERY,  // the XOF, then the query
+  GEN64,      // Field64 (Prio3Count): k_prep_gen
+};
+// PAIR, WIDE and SUM have a launch_* of their own that may decline: then k_xofd, k_query_ps, k_query
+enum class XofKernel : uint8_t { NONE, PAIR, XOFD, XOF, XOF_A_JRPART };
+enum class QueryKernel : uint8_t { NONE, FPW, FP, WIDE, H, PS, SUM, GENERIC };
+enum class RedoFamily : uint8_t { NONE, QH, SUM, GEN64 };  // the run's k_slow_redo* launch
+struct PrepPlan {
+  PrepChain chain;
+  XofKernel xof;
+  QueryKernel query;
+  bool fusable;      // the accumulate can ride on this instance's XOF (what callers pass as fuse)
+  bool dual;         // the share spans two joint-rand blocks: the dual-state XOF
+  bool trunc_xof;    // the XOF's squeeze also truncates / decodes the output share
+  bool slow_defer;   // the query skips flagged reports; the redo launch takes them
+  RedoFamily redo;
+  bool redo_list;    // k_prep_h lists its flagged reports and the redo launch walks the list
+  bool pair;         // Histogram on lane pairs (k_prep_hp)
+  bool pull_in_xof;  // the fused launch copies the leader prep shares itself (else k_pull)
+  uint32_t chunks, chunk_cols;  // stream-overlapped column ranges (1: one launch chain)
+};
+// pulling: the caller hands over mapped host staging to copy from (executor groups)
+PrepPlan plan_prepare(const prio3_engine* e, const DevParams& dp, uint32_t n, bool fuse,
+                      bool pulling);
+inline bool prepare_fuses(const prio3_engine* e) {
+  return plan_prepare(e, e->dp, 0, false, false).fusable;
+}
+// The leader's prepare_init.  soa_staging and the K_LEADER_PREP chain differ by the former's
+// leader_share_len term: both answers are kept as they were.
+enum class LeaderChain : uint8_t { FPVEC, MP64, K_LEADER_PREP, SUM, GENERIC };
+struct LeaderPlan {
+  LeaderChain chain;
+  bool soa_staging;  // k_leader_prep can read the input shares from SoA staging (InPtrs::lin_ld)
+  bool fuse_acc;     // the accumulate rides on k_leader_prep (option leader_fuse_acc)
+};
+LeaderPlan plan_leader(const prio3_engine* e);
 // the helper's kernel chain over the whole run
 int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st, bool fuse,
                 bool allow_chunks, const PullRanges* pull = nullptr);

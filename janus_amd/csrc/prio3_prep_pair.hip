@@ -551,7 +551,7 @@ bool launch_prep_pair(const DevParams& p, InPtrs in, Scratch sc, OutPtrs out, hi
 // most 16 (the wires split 8 / 8); pull: whole 32-report waves and at most two 1 KiB rows of
 // leader-share pieces per share-loop iteration
 bool prep_pair_takes(const DevParams& p, bool pull) {
-  const uint32_t B = (42 + p.meas_len * 16) / 168;
+  const uint32_t B = jr_share_blocks(p.meas_len);
   if (p.es != 16 || p.kind != PRIO3_HISTOGRAM || p.P != 32 || !p.jr_len || B < 2 ||
       p.calls > 16 || p.chunk > 16 || p.arity != 2 * p.chunk)
     return false;

@@ -2049,11 +2049,102 @@ static void launch_xof_slow(const prio3_engine* e, const DevParams& p, const InP
   k_xof_slow<F><<<slow_blocks(p.n), 64, 0, st>>>(p, in, sc);
 }
 
-// The fused accumulate applies where the output share is the measurement share (Histogram;
-// truncate is the identity) and the joint-rand kernel streams that share.
-bool fusable(const prio3_engine* e) {
-  return e->fuse_acc && e->dp.kind == PRIO3_HISTOGRAM && e->dp.jr_len &&
-         (42 + e->dp.meas_len * 16) / 168 >= 2;
+// The one dispatch from a run-time value to a template argument of the prepare kernels:
+// f(std::integral_constant<int, V>{}) for the first V of the list that equals v, else for the last.
+// <32, 16, 8>: PP of k_query_h, k_slow_redo and k_leader_prep; <16, 32, 64, 128>: the P of
+// k_prep_sum and k_slow_redo_sum, whose NPH is P / 16; <1, 0>: a bool.
+template <int V, int... Vs, class F>
+static void with_value(uint32_t v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0)
+    f(std::integral_constant<int, V>{});
+  else if (v == V)
+    f(std::integral_constant<int, V>{});
+  else
+    with_value<Vs...>(v, f);
+}
+
+// The one statement of which kernels a helper prepare takes; pure.
+PrepPlan plan_prepare(const prio3_engine* e, const DevParams& dp, uint32_t n, bool fuse,
+                      bool pulling) {
+  PrepPlan p{};
+  const bool ps = dp.kind == PRIO3_HISTOGRAM || dp.kind == PRIO3_SUMVEC;
+  const bool two = share_spans_two_blocks(dp.meas_len);
+  // The fused accumulate applies where the output share is the measurement share (Histogram;
+  // truncate is the identity) and the joint-rand kernel streams that share.
+  p.fusable = e->fuse_acc && dp.kind == PRIO3_HISTOGRAM && dp.jr_len && two;
+  if (dp.kind == PRIO3_SUMVEC_F64_MP) {
+    p.chain = PrepChain::MP64;
+  } else if (dp.kind == PRIO3_FPVEC_BOUNDED_L2) {
+    // the lane-pair XOF (k_xof_pair, the entries decoded as the share is squeezed), else the
+    // dual-state k_xofd; both decode the entries (the output share) on the fly
+    p.chain = PrepChain::FPVEC;
+    p.dual = p.trunc_xof = two;
+    p.xof = two ? XofKernel::PAIR : XofKernel::XOF;
+    p.query = !e->force_generic && fpvec_query_wide_takes(dp) ? QueryKernel::FPW : QueryKernel::FP;
+  } else if (dp.es != 16) {  // Field64 (Prio3Count): XOF + query in one launch
+    p.chain = PrepChain::GEN64;
+    p.slow_defer = true;
+    p.redo = RedoFamily::GEN64;
+  } else {
+    p.dual = dp.jr_len && two;
+    // XOF + query in one launch: Prio3Sum (k_prep_sum) and Histogram / SumVec with P = 32
+    // (k_prep_h); the slow path of both is deferred to the run's redo launch
+    if (!e->force_generic && p.dual && dp.kind == PRIO3_SUM && !fuse && query_sum_takes(dp)) {
+      p.chain = PrepChain::FUSED_SUM;
+      p.redo = RedoFamily::SUM;
+    } else if (!e->force_generic && p.dual && ps && dp.P == 32) {
+      p.chain = PrepChain::FUSED_H;
+      p.redo = RedoFamily::QH;
+    } else {
+      // two kernels: the XOF (dual-state k_xofd when the share spans >= 2 joint-rand blocks, else
+      // k_xof_a + k_jrpart), then the query
+      p.chain = PrepChain::XOF_QUERY;
+      p.xof = p.dual ? XofKernel::XOFD : XofKernel::XOF_A_JRPART;
+      // P = 64 / 128 on eight lanes per report (k_query_w)
+      const bool wide = ps && !e->force_generic && dp.P != 32 && query_wide_takes(dp);
+      // SumVec under k_query_w: the truncation rides on the XOF's squeeze (the query then reads
+      // the share once)
+      p.trunc_xof = dp.kind == PRIO3_SUMVEC && wide && p.dual && !fuse;
+      // k_query_h defers flagged reports to the run's redo pass; the other queries read the
+      // shares the k_xof_slow launch rewrote
+      const bool qh = ps && !e->force_generic && !wide && (dp.P == 32 || dp.P == 16 || dp.P == 8);
+      if (qh) p.redo = RedoFamily::QH;
+      const bool qsum = !ps && !e->force_generic && query_sum_takes(dp);
+      p.query = wide   ? QueryKernel::WIDE
+                : qh   ? QueryKernel::H
+                : ps   ? QueryKernel::PS
+                : qsum ? QueryKernel::SUM
+                       : QueryKernel::GENERIC;
+    }
+    p.slow_defer = p.redo != RedoFamily::NONE;
+  }
+  const bool fused_h = p.chain == PrepChain::FUSED_H;
+  // k_prep_h can pull the leader prep shares inside its XOF (the query reads them only after the
+  // same lane's XOF): 16-byte pieces over the B - 1 iterations of the share loop, whole waves only
+  // (the executor pads its groups to 64 columns for these instances).
+  p.pull_in_xof = pulling && fused_h && dp.prep_share_len % 16 == 0 &&
+                  dp.prep_share_len / 16 <= 2 * (jr_share_blocks(dp.meas_len) - 1) && n % 64 == 0;
+  // small Histogram runs (the executor's groups) on lane pairs: twice the waves, half the work each
+  if (fused_h && e->pair_max > 0 && n != 0 && n <= (uint32_t)e->pair_max) {
+    DevParams d = dp;
+    d.n = n;
+    p.pair = prep_pair_takes(d, p.pull_in_xof);
+  }
+  p.redo_list = fused_h && !p.pair;
+  // Option "chunks" > 1 (auto: one chunk per 128Ki reports on the two-kernel chain, measured best
+  // on MI355X at 1Mi reports: 8 chunks +4-5% over 1; 16: slower); one launch for the fused kernels
+  // (A/B on MI355X, 1 Mi reports: 169.9 M/s at 1 chunk vs 163.2 M/s at 8) and for the one-kernel
+  // multiproof prepare (1 M reports: 93.1-93.3 M/s at 1 chunk vs 89.0-91.5 at 8, r04e2)
+  const bool one_launch = fused_h || p.chain == PrepChain::FUSED_SUM || p.chain == PrepChain::MP64;
+  const uint32_t K = e->chunks > 0 ? (uint32_t)e->chunks
+                     : one_launch  ? 1u
+                                   : std::max(1u, (n + (1u << 16)) >> 17);
+  p.chunk_cols = ((n + K - 1) / K + 255) & ~255u;
+  p.chunks = p.pair || p.pull_in_xof || K == 1 || n <= p.chunk_cols ||
+                     p.chain == PrepChain::FPVEC
+                 ? 1u
+                 : (n + p.chunk_cols - 1) / p.chunk_cols;
+  return p;
 }
 
 // side streams + their join events and the fork event, created once per engine
@@ -2070,32 +2161,19 @@ static int ensure_side_streams(prio3_engine* e) {
   return PRIO3_OK;
 }
 
-// The helper chain of this instance is the fused k_prep_h (dual-state XOF + k_query_h<2, 32>
-// in one launch; the conditions under which launch_prepare would launch exactly those two).
-static bool prep_fused_takes(const prio3_engine* e, const DevParams& dp, bool fuse) {
-  if (e->force_generic) return false;
-  const bool ps = dp.kind == PRIO3_HISTOGRAM || dp.kind == PRIO3_SUMVEC;
-  const bool dual = dp.es == 16 && dp.jr_len && (42 + dp.meas_len * 16) / 168 >= 2;
-  if (dp.kind == PRIO3_SUM) return dual && !fuse && query_sum_takes(dp);  // k_prep_sum
-  return ps && dual && dp.P == 32;                                         // k_prep_h
-}
-
-// which query family deferred the slow path of its flagged reports (launch_slow_redo redoes them)
-// DEFER_QH_LIST: k_prep_h, which lists its flagged reports (Scratch::redo_cnt, when not null)
-enum : int { DEFER_NONE = 0, DEFER_QH = 1, DEFER_SUM = 2, DEFER_GEN64 = 3, DEFER_QH_LIST = 4 };
 constexpr uint32_t REDO_LIST_BLOCKS = 32;
-// *deferred: set when a query kernel of this chain skipped flagged reports (slow_defer); the
-// caller then ends the run with launch_slow_redo
-// in.leader_src (executor groups, pulls_in_xof): the leader prep shares are still in the mapped
-// host staging and the fused k_prep_h<.., PULL> copies them lane by lane during its XOF.
-// pair: Histogram on lane pairs (k_prep_hp, prio3_prep_pair.hip) instead of k_prep_h
-static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, uint32_t n,
-                          InPtrs in, OutPtrs out, Scratch sc, hipStream_t st, bool fuse,
-                          int* deferred, bool pair = false) {
+// The plan's chain over columns [c0, c0 + n) of the run.  Where the plan defers the slow path
+// (slow_defer), the caller ends the run with launch_slow_redo.
+// plan.pull_in_xof: the leader prep shares are still in the mapped host staging (in.leader_src)
+// and the fused k_prep_h<.., PULL> copies them lane by lane during its XOF.
+static int launch_prepare(prio3_engine* e, const PrepPlan& plan, const DevParams& base,
+                          uint32_t c0, uint32_t n, InPtrs in, OutPtrs out, Scratch sc,
+                          hipStream_t st, bool fuse) {
   DevParams dp = base;
   dp.n = n;
   dp.force_slow = (uint32_t)e->force_slow;
-  dp.slow_defer = 0;
+  dp.trunc_xof = plan.trunc_xof;
+  dp.slow_defer = plan.slow_defer;
   dp.redo = 0;
   const size_t es = dp.es;
   in.nonces += 16 * (size_t)c0;
@@ -2118,19 +2196,19 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
   sc.redo_c0 = c0;
   const uint32_t blocks = (n + 255) / 256;
   const uint32_t xblocks = (n + XOFD_BLOCK - 1) / XOFD_BLOCK;  // k_prep_h, k_xofd
-  if (dp.kind == PRIO3_SUMVEC_F64_MP) {
+  if (plan.chain == PrepChain::MP64) {
     int rc = PRIO3_OK;
     TIMED(e, st, "k_mp64_prepare", (rc = launch_mp64(e, n, dp.ld, in, out, sc, st)));
     return rc;
   }
-  if (dp.kind == PRIO3_FPVEC_BOUNDED_L2) {
+  if (plan.chain == PrepChain::FPVEC) {
     // Sub-batches of dp.ld reports through the per-report scratch (the whole batch's meas
     // shares would not fit: 2.56 MB per report at 10^4 entries); output shares keep one
     // column per report of the batch (ld_out), so accumulate runs once over all of them.
     // Equal sub-batches, cut at whole query rounds (fp_sub_sizes): per-lane latency, not lane
     // count, sets a launch's duration.
     uint32_t nsub, sub;
-    const bool qwide = !e->force_generic && fpvec_query_wide_takes(dp);
+    const bool qwide = plan.query == QueryKernel::FPW;
     fp_sub_sizes(e, n, dp.ld, qwide, nsub, sub);
     for (uint32_t si = 0; si < nsub; si++) {
       const uint32_t s0 = si * sub;
@@ -2148,17 +2226,14 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
       Scratch qs = sc;
       qs.out = (uint8_t*)sc.out + es * s0;
       const uint32_t qb = (q.n + 255) / 256;
-      // the lane-pair XOF (k_xof_pair, the entries decoded as the share is squeezed), else the
-      // dual-state k_xofd; both decode the entries (the output share) on the fly
-      const bool dual = (42 + dp.meas_len * 16) / 168 >= 2;
-      q.trunc_xof = dual ? 1u : 0u;
       bool paired = false;
-      if (dual) TIMED(e, st, "k_xof_pair", (paired = launch_xof_pair(q, qi, qs, st)));
-      if (!paired && dual)
+      if (plan.xof == XofKernel::PAIR)
+        TIMED(e, st, "k_xof_pair", (paired = launch_xof_pair(q, qi, qs, st)));
+      if (!paired && plan.dual)
         TIMED(e, st, "k_xofd",
               (k_xofd<false, true><<<(q.n + XOFD_BLOCK - 1) / XOFD_BLOCK, XOFD_BLOCK, 0, st>>>(
                   q, qi, qs)));
-      else if (!paired)
+      else if (!paired)  // one-block share: no valid FPVec instance (kept as found, untested)
         TIMED(e, st, "k_xof", (k_xof<Fp128><<<qb, 256, 0, st>>>(q, qi, qs)));
       TIMED(e, st, "k_xof_slow", launch_xof_slow<Fp128>(e, q, qi, qs, st));
       if (qwide)
@@ -2168,51 +2243,33 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
     }
     return PRIO3_OK;
   }
-  if (dp.es == 16) {
-    const bool ps = dp.kind == PRIO3_HISTOGRAM || dp.kind == PRIO3_SUMVEC;
-    // P = 64 / 128 on eight lanes per report (k_query_w)
-    const bool wide = ps && !e->force_generic && dp.P != 32 && query_wide_takes(dp);
-    const bool dual = dp.jr_len && (42 + dp.meas_len * 16) / 168 >= 2;
-    // SumVec under k_query_w: the truncation rides on the XOF's squeeze (the query then reads
-    // the share once)
-    dp.trunc_xof = dp.kind == PRIO3_SUMVEC && wide && dual && !fuse ? 1u : 0u;
-    // XOF + query in one launch: Prio3Sum (k_prep_sum) and Histogram / SumVec with P = 32
-    // (k_prep_h); the slow path of both is deferred to the run's redo launch
-    if (prep_fused_takes(e, dp, fuse)) {
-      dp.slow_defer = 1u;
-      if (dp.kind == PRIO3_SUM) {
-        if (deferred) *deferred = DEFER_SUM;
-        switch (dp.P) {
-          case 16: TIMED(e, st, "k_prep_sum", (k_prep_sum<1><<<blocks, 256, 0, st>>>(dp, in, sc, out))); break;
-          case 32: TIMED(e, st, "k_prep_sum", (k_prep_sum<2><<<blocks, 256, 0, st>>>(dp, in, sc, out))); break;
-          case 64: TIMED(e, st, "k_prep_sum", (k_prep_sum<4><<<blocks, 256, 0, st>>>(dp, in, sc, out))); break;
-          default: TIMED(e, st, "k_prep_sum", (k_prep_sum<8><<<blocks, 256, 0, st>>>(dp, in, sc, out))); break;
-        }
-      } else {
-        if (deferred) *deferred = DEFER_QH;
-        const bool pl = in.leader_src != nullptr;
-        bool paired = false;
-        if (pair)
-          TIMED(e, st, "k_prep_hp", (paired = launch_prep_pair(dp, in, sc, out, st, fuse, pl)));
-        if (!paired && deferred) *deferred = DEFER_QH_LIST;
-        if (paired) {
-        } else if (fuse && pl)
-          TIMED(e, st, "k_prep_h", (k_prep_h<true, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
-        else if (fuse)
-          TIMED(e, st, "k_prep_h", (k_prep_h<true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
-        else if (pl)
-          TIMED(e, st, "k_prep_h", (k_prep_h<false, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
-        else
-          TIMED(e, st, "k_prep_h", (k_prep_h<false><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out)));
-      }
-      return PRIO3_OK;
+  if (plan.chain == PrepChain::GEN64) {
+    TIMED(e, st, "k_prep_gen", (k_prep_gen<Fp64><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+  } else if (plan.chain == PrepChain::FUSED_SUM) {
+    TIMED(e, st, "k_prep_sum", (with_value<16, 32, 64, 128>(dp.P, [&](auto p) {
+            k_prep_sum<decltype(p)::value / 16><<<blocks, 256, 0, st>>>(dp, in, sc, out);
+          })));
+  } else if (plan.chain == PrepChain::FUSED_H) {
+    bool paired = false;
+    if (plan.pair) {
+      // no list on lane pairs, nor for k_prep_h should launch_prep_pair decline (it listed before
+      // the plan; unreachable: the plan asked prep_pair_takes the same question): the redo scans
+      sc.redo_cnt = nullptr;
+      TIMED(e, st, "k_prep_hp",
+            (paired = launch_prep_pair(dp, in, sc, out, st, fuse, plan.pull_in_xof)));
     }
-    // two kernels: the XOF (dual-state k_xofd when the share spans >= 2 joint-rand blocks, else
-    // k_xof_a + k_jrpart), then the query
-    if (dual) {
+    if (!paired)
+      TIMED(e, st, "k_prep_h", (with_value<1, 0>(fuse, [&](auto f) {
+              with_value<1, 0>(plan.pull_in_xof, [&](auto pl) {
+                k_prep_h<decltype(f)::value != 0, decltype(pl)::value != 0>
+                    <<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc, out);
+              });
+            })));
+  } else {
+    if (plan.xof == XofKernel::XOFD) {
       if (fuse)
         TIMED(e, st, "k_xofd", (k_xofd<true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
-      else if (dp.trunc_xof)
+      else if (plan.trunc_xof)
         TIMED(e, st, "k_xofd", (k_xofd<false, true><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
       else
         TIMED(e, st, "k_xofd", (k_xofd<false><<<xblocks, XOFD_BLOCK, 0, st>>>(dp, in, sc)));
@@ -2220,45 +2277,35 @@ static int launch_prepare(prio3_engine* e, const DevParams& base, uint32_t c0, u
       TIMED(e, st, "k_xof_a", (k_xof_a<Fp128><<<blocks, 256, 0, st>>>(dp, in, sc)));
       TIMED(e, st, "k_jrpart", (k_jrpart<false><<<blocks, 256, 0, st>>>(dp, in, sc)));
     }
-    // k_query_h defers flagged reports to the run's redo pass (slow_defer); the other queries
-    // read the shares the k_xof_slow launch rewrote
-    const bool qh_path =
-        ps && !e->force_generic && !wide && (dp.P == 32 || dp.P == 16 || dp.P == 8);
-    dp.slow_defer = qh_path ? 1u : 0u;
-    if (qh_path && deferred) *deferred = DEFER_QH;
-    if (!qh_path) TIMED(e, st, "k_xof_slow", launch_xof_slow<Fp128>(e, dp, in, sc, st));
+    if (!plan.slow_defer) TIMED(e, st, "k_xof_slow", launch_xof_slow<Fp128>(e, dp, in, sc, st));
+    // the queries with a launch_* of their own return false for an instance they do not take:
+    // k_query_ps then stands in for k_query_w, k_query for k_query_sum
     bool done = false;
-    if (wide) TIMED(e, st, "k_query_w", (done = launch_query_wide(dp, in, sc, out, st)));
+    if (plan.query == QueryKernel::WIDE)
+      TIMED(e, st, "k_query_w", (done = launch_query_wide(dp, in, sc, out, st)));
+    else if (plan.query == QueryKernel::SUM)
+      TIMED(e, st, "k_query_sum", (done = launch_query_sum(dp, in, sc, out, st)));
     if (done) {
-    } else if (qh_path && dp.P == 32)
-      TIMED(e, st, "k_query_h", (k_query_h<2, 32><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
-    else if (qh_path && dp.P == 16)
-      TIMED(e, st, "k_query_h", (k_query_h<2, 16><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
-    else if (qh_path && dp.P == 8)
-      TIMED(e, st, "k_query_h", (k_query_h<2, 8><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
-    else if (ps)
+    } else if (plan.query == QueryKernel::H)
+      TIMED(e, st, "k_query_h", (with_value<32, 16, 8>(dp.P, [&](auto pp) {
+              k_query_h<2, decltype(pp)::value><<<blocks, 256, 0, st>>>(dp, in, sc, out);
+            })));
+    else if (plan.query == QueryKernel::WIDE || plan.query == QueryKernel::PS)
       TIMED(e, st, "k_query_ps", (k_query_ps<4><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
-    else {
-      bool qs = false;
-      if (!e->force_generic && query_sum_takes(dp))
-        TIMED(e, st, "k_query_sum", (qs = launch_query_sum(dp, in, sc, out, st)));
-      if (!qs) TIMED(e, st, "k_query", (k_query<Fp128><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
-    }
-  } else {  // Field64 (Prio3Count): XOF + query in one launch, the slow path deferred
-    dp.slow_defer = 1u;
-    if (deferred) *deferred = DEFER_GEN64;
-    TIMED(e, st, "k_prep_gen", (k_prep_gen<Fp64><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
+    else
+      TIMED(e, st, "k_query", (k_query<Fp128><<<blocks, 256, 0, st>>>(dp, in, sc, out)));
   }
   return PRIO3_OK;
 }
 
-// R (nullable): the run, whose fused-aggregate accumulators the k_slow_redo<PP> launch zeroes
-static int launch_slow_redo(prio3_engine* e, const DevParams& base, uint32_t n, InPtrs in,
-                            OutPtrs out, Scratch sc, hipStream_t st, int family, Run* R) {
-  const bool list = family == DEFER_QH_LIST && sc.redo_cnt;
-  if (family == DEFER_QH_LIST) family = DEFER_QH;
+// The run's one redo launch (plan.redo).  R (nullable): the run, whose fused-aggregate
+// accumulators the k_slow_redo<PP> launch zeroes.
+static int launch_slow_redo(prio3_engine* e, const PrepPlan& plan, const DevParams& base,
+                            uint32_t n, InPtrs in, OutPtrs out, Scratch sc, hipStream_t st,
+                            Run* R) {
+  const bool list = plan.redo_list && sc.redo_cnt;
   if (!list) sc.redo_cnt = nullptr;  // (the pair kernel and k_query_h list nothing)
-  const bool clean = R && R->agg64 && family == DEFER_QH;
+  const bool clean = R && R->agg64 && plan.redo == RedoFamily::QH;
   const ZeroRanges z = clean ? fused_first_zero(R) : ZeroRanges{};
   DevParams dp = base;
   dp.n = n;
@@ -2267,21 +2314,16 @@ static int launch_slow_redo(prio3_engine* e, const DevParams& base, uint32_t n, 
   dp.slow_defer = 1;
   dp.redo = 1;
   const uint32_t g = list ? REDO_LIST_BLOCKS : redo_blocks(n);
-  if (family == DEFER_GEN64) {  // k_prep_gen<Fp64>: XOF redo, then the generic query
+  if (plan.redo == RedoFamily::GEN64)  // k_prep_gen<Fp64>: XOF redo, then the generic query
     TIMED(e, st, "k_slow_redo", (k_slow_redo_gen<Fp64><<<g, 64, 0, st>>>(dp, in, sc, out)));
-  } else if (family == DEFER_SUM) {
-    switch (dp.P) {
-      case 16: TIMED(e, st, "k_slow_redo", (k_slow_redo_sum<1><<<g, 64, 0, st>>>(dp, in, sc, out))); break;
-      case 32: TIMED(e, st, "k_slow_redo", (k_slow_redo_sum<2><<<g, 64, 0, st>>>(dp, in, sc, out))); break;
-      case 64: TIMED(e, st, "k_slow_redo", (k_slow_redo_sum<4><<<g, 64, 0, st>>>(dp, in, sc, out))); break;
-      default: TIMED(e, st, "k_slow_redo", (k_slow_redo_sum<8><<<g, 64, 0, st>>>(dp, in, sc, out))); break;
-    }
-  } else if (dp.P == 32)
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<32><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
-  else if (dp.P == 16)
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<16><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
+  else if (plan.redo == RedoFamily::SUM)
+    TIMED(e, st, "k_slow_redo", (with_value<16, 32, 64, 128>(dp.P, [&](auto p) {
+            k_slow_redo_sum<decltype(p)::value / 16><<<g, 64, 0, st>>>(dp, in, sc, out);
+          })));
   else
-    TIMED(e, st, "k_slow_redo", (k_slow_redo<8><<<g, 64, 0, st>>>(dp, in, sc, out, z)));
+    TIMED(e, st, "k_slow_redo", (with_value<32, 16, 8>(dp.P, [&](auto pp) {
+            k_slow_redo<decltype(pp)::value><<<g, 64, 0, st>>>(dp, in, sc, out, z);
+          })));
   if (clean) {
     R->fclean = true;
     R->fgen = 0;
@@ -2295,38 +2337,19 @@ static int launch_slow_redo(prio3_engine* e, const DevParams& base, uint32_t n, 
 // before and after), so one chunk's memory-bound query overlaps the next chunk's VALU-bound
 // Keccak.  Side streams are per engine: callers that may overlap (the executor's concurrent
 // groups) pass allow_chunks = false.
-// The chains whose XOF can pull the leader prep shares (the fused k_prep_h: the query reads them
-// only after the same lane's XOF); the share is copied in 16-byte pieces over the share loop.
-// Every wave must be whole (the executor pads its groups to 64 columns for these instances).
-static bool pulls_in_xof(const prio3_engine* e, const DevParams& dp, bool fuse, uint32_t n) {
-  const uint32_t B = (42 + dp.meas_len * 16) / 168;  // share-loop iterations: B - 1
-  return prep_fused_takes(e, dp, fuse) && dp.kind != PRIO3_SUM && dp.prep_share_len % 16 == 0 &&
-         B >= 2 && dp.prep_share_len / 16 <= 2 * (B - 1) && n % 64 == 0;
-}
-
-// Histogram (P = 32) runs of at most pair_max reports on lane pairs (k_prep_hp)
-static bool pair_takes(const prio3_engine* e, const DevParams& base, uint32_t n, bool fuse,
-                       bool pulling) {
-  if (e->pair_max <= 0 || n == 0 || n > (uint32_t)e->pair_max || !prep_fused_takes(e, base, fuse))
-    return false;
-  DevParams d = base;
-  d.n = n;
-  return prep_pair_takes(d, pulling);
-}
-
 // pull (nullable; executor groups): copies the leader prep shares (and the fix-up inputs) from
 // the mapped host staging into the run -- inside the fused XOF + query launch where the chain is
-// k_prep_h (pulls_in_xof), else by one copy launch ahead of the chain.
+// k_prep_h (plan.pull_in_xof), else by one copy launch ahead of the chain.
 int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st, bool fuse,
                 bool allow_chunks, const PullRanges* pull) {
   const uint32_t n = R->n;
-  if (pull && pulls_in_xof(e, R->dp, fuse, n)) {
+  const PrepPlan plan = plan_prepare(e, R->dp, n, fuse, pull != nullptr);
+  if (plan.pull_in_xof) {
     in.leader_src = pull->src[0];
     in.seg_src = (const uint32_t*)pull->src[1];
     in.seg_dst = (uint32_t*)pull->dst[1];
     in.accept_src = pull->src[2];
     in.accept_dst = pull->dst[2];
-    allow_chunks = false;
   } else if (pull) {
     if (!launch_pull(*pull, 256, st)) return PRIO3_EDEVICE;
   }
@@ -2337,7 +2360,7 @@ int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st,
   // k_prep_h chains list their flagged reports for the redo launch (in the stream's zero words)
   // and hold the stream's mutex until the redo launch is enqueued
   std::unique_lock<std::mutex> zlock;
-  if (R->redo_list && prep_fused_takes(e, R->dp, fuse) && R->dp.kind != PRIO3_SUM) {
+  if (R->redo_list && plan.chain == PrepChain::FUSED_H) {
     std::mutex* zmu = nullptr;
     if (uint32_t* zw = stream_zero_words(R->device, st, &zmu)) {
       zlock = std::unique_lock<std::mutex>(*zmu);
@@ -2346,39 +2369,29 @@ int prepare_run(prio3_engine* e, Run* R, InPtrs in, OutPtrs out, hipStream_t st,
     }
   }
   R->last = st;
-  // small Histogram runs (the executor's groups) on lane pairs: twice the waves, half the work each
-  const bool pair = pair_takes(e, R->dp, n, fuse, in.leader_src != nullptr);
-  R->wshift = pair ? 5u : 6u;
-  // auto: one chunk per 128Ki reports on the two-kernel chain; one launch for the fused k_prep_h
-  // (A/B on MI355X, 1 Mi reports: 169.9 M/s at 1 chunk vs 163.2 M/s at 8) and for the one-kernel
-  // multiproof prepare (1 M reports: 93.1-93.3 M/s at 1 chunk vs 89.0-91.5 at 8, r04e2)
-  const uint32_t K = e->chunks > 0 ? (uint32_t)e->chunks
-                     : (prep_fused_takes(e, R->dp, fuse) || R->dp.kind == PRIO3_SUMVEC_F64_MP)
-                         ? 1u
-                         : std::max(1u, (n + (1u << 16)) >> 17);
-  const uint32_t csz = ((n + K - 1) / K + 255) & ~255u;
-  int deferred = DEFER_NONE;
-  if (pair || !allow_chunks || K == 1 || n <= csz || R->dp.kind == PRIO3_FPVEC_BOUNDED_L2) {
-    const int rc = launch_prepare(e, R->dp, 0, n, in, out, sc, st, fuse, &deferred, pair);
-    if (rc == PRIO3_OK && deferred)
-      return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred, R);
+  R->wshift = plan.pair ? 5u : 6u;
+  if (!allow_chunks || plan.chunks == 1) {
+    const int rc = launch_prepare(e, plan, R->dp, 0, n, in, out, sc, st, fuse);
+    if (rc == PRIO3_OK && plan.redo != RedoFamily::NONE)
+      return launch_slow_redo(e, plan, R->dp, n, in, out, sc, st, R);
     return rc;
   }
   int rc = ensure_side_streams(e);
   if (rc) return rc;
   HIPCHK(hipEventRecord(e->fork_ev, st));
   for (auto s2 : e->side) HIPCHK(hipStreamWaitEvent(s2, e->fork_ev, 0));
+  const uint32_t csz = plan.chunk_cols;
   uint32_t c = 0;
   for (uint32_t c0 = 0; c0 < n; c0 += csz, c++) {
-    rc = launch_prepare(e, R->dp, c0, std::min(csz, n - c0), in, out, sc, e->side[c % 2], fuse,
-                        &deferred);
+    rc = launch_prepare(e, plan, R->dp, c0, std::min(csz, n - c0), in, out, sc, e->side[c % 2],
+                        fuse);
     if (rc) return rc;
   }
   for (size_t i = 0; i < e->side.size(); i++) {
     HIPCHK(hipEventRecord(e->side_ev[i], e->side[i]));
     HIPCHK(hipStreamWaitEvent(st, e->side_ev[i], 0));
   }
-  if (deferred) return launch_slow_redo(e, R->dp, n, in, out, sc, st, deferred, R);
+  if (plan.redo != RedoFamily::NONE) return launch_slow_redo(e, plan, R->dp, n, in, out, sc, st, R);
   return PRIO3_OK;
 }
 
@@ -2420,13 +2433,26 @@ static int leader_init_fpvec(prio3_engine* e, Run* R, const uint8_t* d_nonces,
   return PRIO3_OK;
 }
 
-// The instances whose leader prepare_init is one k_leader_prep launch (the only leader kernel that
-// reads the leader input shares from SoA staging, InPtrs::lin_ld)
-bool leader_prep_takes(const prio3_engine* e) {
-  const DevParams& dp = e->dp;
-  return e->leader_fast && (dp.kind == PRIO3_HISTOGRAM || dp.kind == PRIO3_SUMVEC) && dp.jr_len &&
-         (dp.P == 32 || dp.P == 16 || dp.P == 8) &&
-         dp.leader_share_len == 16 * (dp.meas_len + dp.proof_len + 1);
+// The one statement of which kernels the leader's prepare_init takes.
+LeaderPlan plan_leader(const prio3_engine* e) {
+  const DevParams& d = e->dp;
+  LeaderPlan p{};
+  // the helper kernels in their leader role: one k_leader_prep launch
+  const bool prep = e->leader_fast && (d.kind == PRIO3_HISTOGRAM || d.kind == PRIO3_SUMVEC) &&
+                    d.jr_len && (d.P == 32 || d.P == 16 || d.P == 8);
+  const bool sum = d.kind == PRIO3_SUM && e->leader_fast && query_sum_takes(d);
+  p.chain = d.kind == PRIO3_FPVEC_BOUNDED_L2 ? LeaderChain::FPVEC
+            : d.kind == PRIO3_SUMVEC_F64_MP  ? LeaderChain::MP64
+            : prep                           ? LeaderChain::K_LEADER_PREP
+            : sum                            ? LeaderChain::SUM
+                                             : LeaderChain::GENERIC;
+  // k_leader_prep is the only leader kernel that reads the input shares from SoA staging
+  // (InPtrs::lin_ld); the staging takes that form only for a share without trailing bytes
+  p.soa_staging = prep && d.leader_share_len == 16 * (d.meas_len + d.proof_len + 1);
+  // Device leader init with the accumulate fused into k_leader_prep (option leader_fuse_acc):
+  // Histogram, whose output share is the measurement share that leader_jr_body streams through
+  p.fuse_acc = e->leader_fuse_acc && prep && d.kind == PRIO3_HISTOGRAM && d.es == 16;
+  return p;
 }
 
 // vk_slot / vk_tab (nullable): per-report verify keys of a coalesced group of several tasks
@@ -2434,87 +2460,57 @@ int leader_init_run(prio3_engine* e, Run* R, const uint8_t* d_nonces,
                     const uint8_t* d_public_shares, const uint8_t* d_leader_input_shares,
                     uint8_t* d_prep_shares, uint8_t* d_status, hipStream_t st,
                     const uint16_t* vk_slot, const uint4* vk_tab, uint32_t lin_ld) {
+  const LeaderPlan plan = plan_leader(e);
   DevParams dp = R->dp;
   dp.force_slow = (uint32_t)e->force_slow;
   const uint32_t n = R->n;
   R->last = st;
-  if (dp.kind == PRIO3_FPVEC_BOUNDED_L2)
-    return leader_init_fpvec(e, R, d_nonces, d_public_shares, d_leader_input_shares,
-                             d_prep_shares, d_status, st);
-  if (dp.kind == PRIO3_SUMVEC_F64_MP) {
-    int rc = PRIO3_OK;
-    TIMED(e, st, "k_mp64_prepare",
-          (rc = launch_mp64_leader(e, n, dp.ld, InPtrs{d_nonces, d_public_shares,
-                                                       d_leader_input_shares, nullptr},
-                                   OutPtrs{d_prep_shares, d_status}, R->sc, st)));
-    return rc;
+  InPtrs in{d_nonces, d_public_shares, d_leader_input_shares, nullptr};
+  OutPtrs out{d_prep_shares, d_status};
+  int rc = PRIO3_OK;
+  switch (plan.chain) {
+    case LeaderChain::FPVEC:
+      return leader_init_fpvec(e, R, d_nonces, d_public_shares, d_leader_input_shares,
+                               d_prep_shares, d_status, st);
+    case LeaderChain::MP64:
+      TIMED(e, st, "k_mp64_prepare", (rc = launch_mp64_leader(e, n, dp.ld, in, out, R->sc, st)));
+      return rc;
+    case LeaderChain::GENERIC:
+      TIMED(e, st, "k_leader_init",
+            rc = launch_leader_init(dp, d_nonces, d_public_shares, d_leader_input_shares, R->sc,
+                                    d_prep_shares, d_status, st, vk_slot, vk_tab));
+      return rc;
+    default: break;
   }
-  const bool ps = dp.kind == PRIO3_HISTOGRAM || dp.kind == PRIO3_SUMVEC;
-  if (ps && dp.jr_len && (dp.P == 32 || dp.P == 16 || dp.P == 8) && e->leader_fast) {
-    // the helper kernels in their leader role
-    InPtrs in{d_nonces, d_public_shares, d_leader_input_shares, nullptr};
-    in.vk_slot = vk_slot;
-    in.vk_tab = vk_tab;
+  in.vk_slot = vk_slot;
+  in.vk_tab = vk_tab;
+  const uint32_t blocks = (n + 255) / 256, blocks64 = (n + 63) / 64;
+  if (plan.chain == LeaderChain::K_LEADER_PREP) {
     in.lin_ld = lin_ld;
-    OutPtrs out{d_prep_shares, d_status};
-    const uint32_t blocks = (n + 255) / 256, blocks64 = (n + 63) / 64;
     // R->lfused: the wave partials of the share for segment 0, fixed up at accumulate
     uint32_t* wp = R->lfused ? R->wpart : nullptr;
     uint32_t* wsg = R->lfused ? R->wseg : nullptr;
     // one launch; flagged reports redone after k_leader_slowfix
     DevParams d1 = dp;
     d1.slow_defer = 1;
-    if (dp.P == 32)
-      TIMED(e, st, "k_leader_prep",
-            (k_leader_prep<32><<<blocks, 256, 0, st>>>(d1, in, R->sc, out, wp, wsg)));
-    else if (dp.P == 16)
-      TIMED(e, st, "k_leader_prep",
-            (k_leader_prep<16><<<blocks, 256, 0, st>>>(d1, in, R->sc, out, wp, wsg)));
-    else
-      TIMED(e, st, "k_leader_prep",
-            (k_leader_prep<8><<<blocks, 256, 0, st>>>(d1, in, R->sc, out, wp, wsg)));
+    TIMED(e, st, "k_leader_prep", (with_value<32, 16, 8>(dp.P, [&](auto pp) {
+            k_leader_prep<decltype(pp)::value><<<blocks, 256, 0, st>>>(d1, in, R->sc, out, wp, wsg);
+          })));
     dp.redo = 1;
-    TIMED(e, st, "k_leader_slowfix",
-          (k_leader_slowfix<<<blocks64, 64, 0, st>>>(dp, in, R->sc)));
-    if (dp.P == 32)
-      TIMED(e, st, "k_query_h", (k_query_h<2, 32, 1><<<blocks, 256, 0, st>>>(dp, in, R->sc, out)));
-    else if (dp.P == 16)
-      TIMED(e, st, "k_query_h", (k_query_h<2, 16, 1><<<blocks, 256, 0, st>>>(dp, in, R->sc, out)));
-    else
-      TIMED(e, st, "k_query_h", (k_query_h<2, 8, 1><<<blocks, 256, 0, st>>>(dp, in, R->sc, out)));
+    TIMED(e, st, "k_leader_slowfix", (k_leader_slowfix<<<blocks64, 64, 0, st>>>(dp, in, R->sc)));
+    TIMED(e, st, "k_query_h", (with_value<32, 16, 8>(dp.P, [&](auto pp) {
+            k_query_h<2, decltype(pp)::value, 1><<<blocks, 256, 0, st>>>(dp, in, R->sc, out);
+          })));
     return PRIO3_OK;
   }
-  if (dp.kind == PRIO3_SUM && e->leader_fast && query_sum_takes(dp)) {
-    // Prio3Sum: the same unpack / joint-rand kernels, then k_query_sum in its leader role
-    InPtrs in{d_nonces, d_public_shares, d_leader_input_shares, nullptr};
-    in.vk_slot = vk_slot;
-    in.vk_tab = vk_tab;
-    OutPtrs out{d_prep_shares, d_status};
-    const uint32_t blocks = (n + 255) / 256, blocks64 = (n + 63) / 64;
-    // (leader_jr_body's per-lane row streaming loses here: the short share leaves little Keccak
-    // to hide the 1.6 KB rows' uncoalesced reads -- 2.63 against 1.30 + 0.46 ms per 1.25 M)
-    TIMED(e, st, "k_leader_unpack",
-          (k_leader_unpack<<<(n + 63) / 64, 256, 0, st>>>(dp, in, R->sc, d_status, nullptr,
-                                                         nullptr)));
-    TIMED(e, st, "k_jrpart", (k_jrpart<false, true><<<blocks, 256, 0, st>>>(dp, in, R->sc)));
-    TIMED(e, st, "k_leader_slowfix",
-          (k_leader_slowfix<<<blocks64, 64, 0, st>>>(dp, in, R->sc)));
-    bool ok = false;
-    TIMED(e, st, "k_query_sum", (ok = launch_query_sum(dp, in, R->sc, out, st, true)));
-    return ok ? PRIO3_OK : PRIO3_EDEVICE;
-  }
-  int rc2 = PRIO3_OK;
-  TIMED(e, st, "k_leader_init",
-        rc2 = launch_leader_init(dp, d_nonces, d_public_shares, d_leader_input_shares, R->sc,
-                                 d_prep_shares, d_status, st, vk_slot, vk_tab));
-  return rc2;
-}
-
-// Device leader init with the accumulate fused into k_leader_prep (option leader_fuse_acc):
-// Histogram on the helper kernels' leader role, whose output share is the measurement share
-// that leader_jr_body streams through anyway.
-bool leader_fuse_takes(const prio3_engine* e) {
-  const DevParams& d = e->dp;
-  return e->leader_fuse_acc && e->leader_fast && d.jr_len && d.kind == PRIO3_HISTOGRAM &&
-         (d.P == 32 || d.P == 16 || d.P == 8) && !own_out(d) && d.es == 16;
+  // Prio3Sum: the same unpack / joint-rand kernels, then k_query_sum in its leader role
+  // (leader_jr_body's per-lane row streaming loses here: the short share leaves little Keccak
+  // to hide the 1.6 KB rows' uncoalesced reads -- 2.63 against 1.30 + 0.46 ms per 1.25 M)
+  TIMED(e, st, "k_leader_unpack",
+        (k_leader_unpack<<<blocks64, 256, 0, st>>>(dp, in, R->sc, d_status, nullptr, nullptr)));
+  TIMED(e, st, "k_jrpart", (k_jrpart<false, true><<<blocks, 256, 0, st>>>(dp, in, R->sc)));
+  TIMED(e, st, "k_leader_slowfix", (k_leader_slowfix<<<blocks64, 64, 0, st>>>(dp, in, R->sc)));
+  bool ok = false;
+  TIMED(e, st, "k_query_sum", (ok = launch_query_sum(dp, in, R->sc, out, st, true)));
+  return ok ? PRIO3_OK : PRIO3_EDEVICE;
 }

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TR ? 4 : 5,
 
 // long-share joint-randomness instances (SumVec / FPVec): true if launched
 bool launch_xof_pair(const DevParams& p, InPtrs in, Scratch sc, hipStream_t st) {
-  if (p.es != 16 || !p.jr_len || (42 + p.meas_len * 16) / 168 < 2) return false;
+  if (p.es != 16 || !p.jr_len || !share_spans_two_blocks(p.meas_len)) return false;
   if (p.trunc_xof)
     k_xof_pair<true><<<(p.n + 127) / 128, 256, 0, st>>>(p, in, sc);
   else

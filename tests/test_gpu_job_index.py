@@ -290,7 +290,7 @@ def test_chain_into_prepare_aggregate(oracle_lib):
     aggregate_finish_device -> batch_metadata_device, all on one stream without a host round trip,
     against the same three calls fed the restatement's segment ids and accept mask.  Segments 3-7
     are empty (count 0, checksum 0, Interval::EMPTY).
-    Path: Histogram(10, 3) is below the fused accumulate's size (fusable() asks for a measurement
+    Path: Histogram(10, 3) is below the fused accumulate's size (PrepPlan::fusable wants a measurement
     of at least 19 elements), so prio3_device_prepare_aggregate defers the sum to the finish call's
     one-pass segmented reduction (run_accumulate, k_acc_seg); with 8 segments that is its
     8-segments-per-block instance, where 2-4 segments take the 4-segment one.  The existing
