@@ -146,7 +146,8 @@ typedef struct {
 /* Fills out[0 .. min(cap, members)) and returns the member count (1 for a one-GPU engine). */
 int prio3_engine_members(const prio3_engine* engine, prio3_member_info* out, uint32_t cap);
 /* Counters of one executor a member's jobs use (shared with every engine of the same instance on
- * that GPU): kind 0 helper prepare, 1 accumulate, 2 leader prepare_init, 3 leader prepare_next. */
+ * that GPU): kind 0 helper prepare, 1 accumulate, 2 leader prepare_init, 3 leader prepare_next,
+ * 5 leader upload (4 is the HPKE open's, janus_hpke_executor_stats_get). */
 typedef struct {
   uint64_t jobs, reports;  /* submitted since the process started */
   uint64_t groups;         /* launches */
@@ -707,6 +708,76 @@ int prio3_leader_upload_batch(
     uint8_t* helper_config_ids, uint8_t* helper_enc, uint32_t helper_enc_len, uint8_t* helper_ct,
     uint32_t* helper_ct_len, uint32_t helper_ct_stride, uint8_t* leader_config_ids,
     uint8_t* status);
+/* The job form: prio3_leader_upload_batch through the upload executor (kind 5 of
+ * prio3_executor_stats_get / prio3_executor_control).  Concurrent jobs -- of any task, each with its
+ * own task ID, now, report_deadline, task_expiration and report_expiry_age -- share one launch chain
+ * when they name the same two openers and config IDs, the same report_stride, ext_stride,
+ * helper_enc_len and helper_ct_stride, and engines of one VDAF instance with the same upload_aead
+ * choice.  Each job copies its rows once, into its group's pinned staging, on the calling thread.
+ * The fields of prio3_upload_job_in are the inputs of prio3_leader_upload_batch under the same names
+ * (task_id: the 32 bytes themselves), those of prio3_upload_job_out its twelve host output pointers,
+ * with the same nullability rules (public_shares, extensions, helper_enc, helper_ct: NULL when their
+ * row length is 0).  Every output is byte for byte what prio3_leader_upload_batch writes for the
+ * same arguments, and so are the return codes: PRIO3_EINVAL for a NULL engine, job or out, both
+ * openers NULL, an opener on another GPU than the engine, report_stride or ext_stride not a multiple
+ * of 4, report_stride >= 2^31, helper_enc_len > 0xFFFF, a missing buffer (n > 0);
+ * PRIO3_EUNSUPPORTED for PRIO3_FPVEC_BOUNDED_L2; n == 0 is PRIO3_OK.
+ * prio3_leader_upload_job_submit is its ticketed twin and obeys the rules of "Ticketed job
+ * submission" above word for word: the inputs -- the rows, the lengths and both structs -- are read
+ * only inside the submit call, the outputs are written only inside prio3_ticket_wait on the waiting
+ * thread, notify_fd is written exactly once per ticket, prio3_ticket_poll never blocks, and the
+ * calling thread's HIP device is left as it was.  The helper's ciphertext rows are cut out of the
+ * job's staged Report rows inside the wait: they cross the link once, inside the Report.
+ * Synchronous paths (prio3_leader_upload_batch runs inside the call, or inside submit with a done
+ * ticket and notify_fd written there): an empty job; a job of more than
+ * PRIO3_UPLOAD_JOB_MAX_REPORTS reports; rows that do not fit one group's staging; an engine with
+ * option coalesce = 0.  No size or instance is refused that the batch form accepts.  A multi-GPU
+ * engine places the job on its least-loaded member on the openers' GPU.
+ * PRIO3_UPLOAD_JOB_MAX_REPORTS: a group's pinned staging is 96 MB and holds, per report, the Report
+ * row and every output row but the helper's (report_stride + public_share_len +
+ * leader_input_share_len + ext_stride + 83 bytes); the limit is 96 MB over the largest such
+ * footprint a job may have and still coalesce whatever its size, 24 KB -- about twice that of a
+ * Histogram(256,16) report (a 5.7 KB row and a 5.6 KB leader share).  A job with a larger footprint
+ * coalesces while n times the footprint is within the staging. */
+enum { PRIO3_UPLOAD_JOB_MAX_REPORTS = 4096 };
+typedef struct {
+  struct janus_hpke_opener* task_opener;   /* nullable (not both) */
+  struct janus_hpke_opener* global_opener; /* nullable (not both) */
+  uint8_t task_config_id;
+  uint8_t global_config_id;
+  uint8_t reserved[2];                     /* 0 */
+  uint32_t n;
+  uint8_t task_id[32];
+  uint64_t now;
+  uint64_t report_deadline;
+  uint64_t task_expiration;                /* UINT64_MAX: none */
+  uint64_t report_expiry_age;              /* UINT64_MAX: none */
+  const uint8_t* reports;                  /* host [n][report_stride] */
+  const uint32_t* report_len;              /* host [n] */
+  uint32_t report_stride;
+  uint32_t ext_stride;
+  uint32_t helper_enc_len;
+  uint32_t helper_ct_stride;
+} prio3_upload_job_in;
+typedef struct {
+  uint8_t* report_ids;                     /* [n][16] */
+  uint64_t* times;                         /* [n] */
+  uint8_t* public_shares;                  /* [n][public_share_len] */
+  uint8_t* leader_input_shares;            /* [n][leader_input_share_len] */
+  uint8_t* extensions;                     /* [n][ext_stride] */
+  uint32_t* ext_len;                       /* [n] */
+  uint8_t* helper_config_ids;              /* [n] */
+  uint8_t* helper_enc;                     /* [n][helper_enc_len] */
+  uint8_t* helper_ct;                      /* [n][helper_ct_stride] */
+  uint32_t* helper_ct_len;                 /* [n] */
+  uint8_t* leader_config_ids;              /* [n] */
+  uint8_t* status;                         /* [n] */
+} prio3_upload_job_out;
+int prio3_leader_upload_job(prio3_engine* engine, const prio3_upload_job_in* job,
+                            const prio3_upload_job_out* out);
+int prio3_leader_upload_job_submit(prio3_engine* engine, const prio3_upload_job_in* job,
+                                   const prio3_upload_job_out* out, int notify_fd,
+                                   prio3_ticket** ticket_out);
 
 /* ---- Client ---- */
 /* The client role of prio::vdaf: Prio3::shard on the caller's measurements (client/src/lib.rs:

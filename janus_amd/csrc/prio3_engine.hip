@@ -582,7 +582,14 @@ int engine_exec_id(const prio3_engine* e) { return e->device * EXEC_LANES + e->l
 // it, and Janus merges the per-job aggregations at collection
 // (/root/reference/aggregator/src/aggregator/aggregation_job_writer.rs:510 writes a random `ord`
 // shard per job; aggregate_share.rs:55-96 sums the shards).
-static prio3_engine* place(prio3_engine* e, uint32_t n) {
+// upload: an upload job -- only the members on e's own GPU (its openers are bound to it), their
+// upload executors' reports counted too; the caller counts the job (placed) once it knows that an
+// executor takes it.
+static void placed(prio3_engine* m, uint32_t n) {
+  m->placed_jobs.fetch_add(1, std::memory_order_relaxed);
+  m->placed_reports.fetch_add(n, std::memory_order_relaxed);
+}
+static prio3_engine* place(prio3_engine* e, uint32_t n, bool upload = false) {
   prio3_engine* best = e;
   const size_t k = e->members.size();
   if (k > 1) {
@@ -590,15 +597,16 @@ static prio3_engine* place(prio3_engine* e, uint32_t n) {
     uint64_t bl = UINT64_MAX;
     for (size_t i = 0; i < k; i++) {
       prio3_engine* m = e->members[(s0 + i) % k];
-      const uint64_t l = exec_load(engine_exec_id(m));
+      if (upload && m->device != e->device) continue;
+      const int id = engine_exec_id(m);
+      const uint64_t l = exec_load(id) + (upload ? exec_upload_load(id) : 0);
       if (l < bl) {
         bl = l;
         best = m;
       }
     }
   }
-  best->placed_jobs.fetch_add(1, std::memory_order_relaxed);
-  best->placed_reports.fetch_add(n, std::memory_order_relaxed);
+  if (!upload) placed(best, n);
   return best;
 }
 
@@ -1613,7 +1621,8 @@ int prio3_executor_stats_get(const prio3_engine* e, uint32_t member, int kind,
 int prio3_executor_control(prio3_engine* e, int which, const char* key, int64_t value) {
   if (!e || !key || which < -1 || which >= EXEC_KINDS) return PRIO3_EINVAL;
   for (size_t i = 0; i < member_count(e); i++)
-    for (int kind : {(int)EXEC_PREP, (int)EXEC_ACC, (int)EXEC_LEADER, (int)EXEC_LNEXT}) {
+    for (int kind : {(int)EXEC_PREP, (int)EXEC_ACC, (int)EXEC_LEADER, (int)EXEC_LNEXT,
+                     (int)EXEC_UPLOAD}) {
       if (which >= 0 && kind != which) continue;
       const int rc = exec_control(kind, member_exec_id(member_at(e, i), kind), key, value);
       if (rc != PRIO3_OK) return rc;
@@ -1892,7 +1901,7 @@ int prio3_device_output_shares(prio3_engine* e, uint32_t n, uint8_t* out) {
 // forms: `tk` is nullptr for the blocking call, which then goes through the executor's blocking
 // submit exactly as before.
 struct prio3_ticket {
-  enum Kind { SYNC, HELPER, LEADER_INIT, LEADER_NEXT };
+  enum Kind { SYNC, HELPER, LEADER_INIT, LEADER_NEXT, UPLOAD };
   Kind kind = SYNC;
   ExecTicket* xt = nullptr;
   prio3_engine* e = nullptr;  // LEADER_INIT: the member the job was placed on, its report count
@@ -1973,6 +1982,11 @@ int prio3_ticket_wait(prio3_ticket* t) {
     }
     case prio3_ticket::LEADER_NEXT: {
       TraceSpan span_("leader VDAF preparation");
+      rc = exec_ticket_complete(t->xt, nullptr);
+      break;
+    }
+    case prio3_ticket::UPLOAD: {
+      TraceSpan span_("handle_upload_generic");
       rc = exec_ticket_complete(t->xt, nullptr);
       break;
     }
@@ -2856,6 +2870,94 @@ int prio3_leader_finish_job_submit(prio3_batch* b, const prio3_leader_job_in* in
   if (!ticket_out) return PRIO3_EINVAL;
   *ticket_out = nullptr;
   return leader_finish_job(b, in, out, notify_fd, ticket_out);
+}
+
+// ---- the leader's upload as an executor job ----
+static int upload_batch_of(prio3_engine* e, const prio3_upload_job_in* in,
+                           const prio3_upload_job_out* out) {
+  return prio3_leader_upload_batch(
+      e, in->task_opener, in->task_config_id, in->global_opener, in->global_config_id, in->n,
+      in->task_id, in->now, in->report_deadline, in->task_expiration, in->report_expiry_age,
+      in->reports, in->report_stride, in->report_len, out->report_ids, out->times,
+      out->public_shares, out->leader_input_shares, out->extensions, out->ext_len, in->ext_stride,
+      out->helper_config_ids, out->helper_enc, in->helper_enc_len, out->helper_ct,
+      out->helper_ct_len, in->helper_ct_stride, out->leader_config_ids, out->status);
+}
+
+static int leader_upload_job(prio3_engine* e, const prio3_upload_job_in* in,
+                             const prio3_upload_job_out* out, int notify_fd, prio3_ticket** tk) {
+  TraceSpan span_("handle_upload_generic");
+  if (!e || !in || !out) return PRIO3_EINVAL;
+  // the argument checks of prio3_leader_upload_batch, in its order
+  if (e->dp.kind == PRIO3_FPVEC_BOUNDED_L2) return PRIO3_EUNSUPPORTED;
+  if ((!in->task_opener && !in->global_opener) || in->report_stride % 4 != 0 ||
+      in->ext_stride % 4 != 0 || in->report_stride >= (1u << 31) || in->helper_enc_len > 0xFFFF)
+    return PRIO3_EINVAL;
+  for (auto* o : {in->task_opener, in->global_opener})
+    if (o && hpke_opener_device(o) != e->device) return PRIO3_EINVAL;
+  const uint32_t n = in->n;
+  if (n == 0) return ticket_sync(PRIO3_OK, notify_fd, tk);
+  if (!in->reports || !in->report_len || !out->report_ids || !out->times ||
+      !out->leader_input_shares || !out->ext_len || !out->helper_config_ids ||
+      !out->helper_ct_len || !out->leader_config_ids || !out->status ||
+      (e->sz.public_share_len && !out->public_shares) || (in->ext_stride && !out->extensions) ||
+      (in->helper_enc_len && !out->helper_enc) || (in->helper_ct_stride && !out->helper_ct))
+    return PRIO3_EINVAL;
+  e = place(e, n, true);
+  UploadJob job;
+  job.e = e;
+  job.op[0] = in->task_opener;
+  job.op[1] = in->global_opener;
+  job.cfg[0] = in->task_config_id;
+  job.cfg[1] = in->global_config_id;
+  for (int p = 0; p < 2; p++) job.wide[p] = job.op[p] && upload_job_wide(e, job.op[p]);
+  job.n = n;
+  memcpy(job.task_id, in->task_id, 32);
+  job.now = in->now;
+  job.deadline = in->report_deadline;
+  job.task_exp = in->task_expiration;
+  job.expiry_age = in->report_expiry_age;
+  job.reports = in->reports;
+  job.report_len = in->report_len;
+  job.stride = in->report_stride;
+  job.ext_stride = in->ext_stride;
+  job.henc_len = in->helper_enc_len;
+  job.hct_stride = in->helper_ct_stride;
+  job.ids = out->report_ids;
+  job.times = out->times;
+  job.pub = out->public_shares;
+  job.shares = out->leader_input_shares;
+  job.ext = out->extensions;
+  job.ext_len = out->ext_len;
+  job.hcfg = out->helper_config_ids;
+  job.henc = out->helper_enc;
+  job.hct = out->helper_ct;
+  job.hct_len = out->helper_ct_len;
+  job.lcfg = out->leader_config_ids;
+  job.status = out->status;
+  // what one group cannot hold, and an engine that does not coalesce: the batch form, here
+  if (!e->coalesce || n > PRIO3_UPLOAD_JOB_MAX_REPORTS ||
+      upload_report_bytes(&job) * n > UPLOAD_STAGING_BYTES)
+    return ticket_sync(upload_batch_of(e, in, out), notify_fd, tk);
+  placed(e, n);
+  if (tk) {
+    ExecTicket* xt = nullptr;
+    return ticket_queued(exec_upload_begin(&job, notify_fd, &xt), prio3_ticket::UPLOAD, xt, tk);
+  }
+  return exec_upload(&job);
+}
+
+int prio3_leader_upload_job(prio3_engine* e, const prio3_upload_job_in* in,
+                            const prio3_upload_job_out* out) {
+  return leader_upload_job(e, in, out, -1, nullptr);
+}
+
+int prio3_leader_upload_job_submit(prio3_engine* e, const prio3_upload_job_in* in,
+                                   const prio3_upload_job_out* out, int notify_fd,
+                                   prio3_ticket** ticket_out) {
+  if (!ticket_out) return PRIO3_EINVAL;
+  *ticket_out = nullptr;
+  return leader_upload_job(e, in, out, notify_fd, ticket_out);
 }
 
 int prio3_trace_enabled(void) { return trace_enabled() ? 1 : 0; }

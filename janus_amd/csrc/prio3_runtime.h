@@ -177,8 +177,11 @@ int exec_submit(ExecJob* job);
 // Executor control and counters (prio3_executor_control / prio3_engine_members): ExecStats of
 // prio3_exec.h.
 // kinds: 0 helper prepare, 1 accumulate, 2 leader prepare_init, 3 leader prepare_next,
-// 4 HPKE open of input shares
-enum { EXEC_PREP = 0, EXEC_ACC = 1, EXEC_LEADER = 2, EXEC_LNEXT = 3, EXEC_HPKE = 4, EXEC_KINDS = 5 };
+// 4 HPKE open of input shares, 5 leader upload
+enum {
+  EXEC_PREP = 0, EXEC_ACC = 1, EXEC_LEADER = 2, EXEC_LNEXT = 3, EXEC_HPKE = 4, EXEC_UPLOAD = 5,
+  EXEC_KINDS = 6
+};
 int exec_stats(int kind, int exec_id, ExecStats* out);
 // hold = 1: the executor's launcher takes no group until hold = 0 (tests pre-queue jobs with
 // it); heavy = reports inside submit at which the launcher switches to its heavy-load form
@@ -504,6 +507,81 @@ int hpke_group_issue(const HpkeJob& proto, const HpkeLayout& L, const uint8_t* s
                      uint32_t n, hipStream_t* st_out, Slab** slab_out, bool own_queue);
 int exec_hpke(HpkeJob* job);
 
+// ---- coalesced leader upload (prio3_leader_upload_job of concurrent jobs) ------------------
+// VdafOps::handle_upload_generic runs once per HTTP request and ReportWriteBatcher collects about
+// 100 accepted reports per write (Janus's aggregator/src/binaries/aggregator.rs:283-284):
+// concurrent upload batches of every task that opens with the same keypairs share one launch
+// chain.  Each staged report carries its length and a job slot (UploadMeta) into the group's job
+// table (UploadJobRow: what differs between the jobs of a group).
+struct UploadJob {
+  prio3_engine* e = nullptr;  // the member the job was placed on
+  janus_hpke_opener* op[2] = {nullptr, nullptr};  // the task's opener, the global one
+  uint8_t cfg[2] = {0, 0};
+  bool wide[2] = {false, false};  // the resolved AEAD kernel per opener (engine option upload_aead)
+  uint32_t n = 0;
+  uint8_t task_id[32] = {0};
+  uint64_t now = 0, deadline = 0, task_exp = 0, expiry_age = 0;
+  const uint8_t* reports = nullptr;  // host [n][stride], read by stage()
+  const uint32_t* report_len = nullptr;
+  uint32_t stride = 0, ext_stride = 0, henc_len = 0, hct_stride = 0;
+  // host outputs (prio3_upload_job_out), written by unstage()
+  uint8_t *ids = nullptr, *pub = nullptr, *shares = nullptr, *ext = nullptr, *hcfg = nullptr;
+  uint8_t *henc = nullptr, *hct = nullptr, *lcfg = nullptr, *status = nullptr;
+  uint64_t* times = nullptr;
+  uint32_t *ext_len = nullptr, *hct_len = nullptr;
+  uint32_t c0 = 0, slot = 0;  // placement in the group: first column, row of the job table
+};
+struct UploadMeta {  // one per staged report
+  uint32_t len;
+  uint16_t slot, pad;
+};
+struct UploadJobRow {  // one per job of a group
+  uint32_t task[8];    // task ID, BE words (the AAD's first two blocks)
+  unsigned long long now, deadline, task_exp, expiry_age;
+};
+constexpr uint32_t UPLOAD_MAX_JOBS = 1024;     // rows of a group's job table (u16 slots)
+constexpr uint32_t UPLOAD_MAX_GROUP = 65536;   // reports per group (a full scratch chunk of the chain)
+// Staging of an upload group with room for cap reports.  Inputs: a head of 256 bytes (the chain's
+// two list counters, staged as zeros), the job table, the per-report meta, then the Report rows --
+// the head, the table and the meta travel in one DMA, the rows in a second.  Outputs: one block
+// the device fills and one DMA returns, its arrays packed for the n reports the group ended with
+// (UploadOut, made at issue time; unstage runs after that).  The helper's ciphertext rows are not
+// among them: unstage cuts them out of the job's own staged rows.
+struct UploadLayout {
+  uint32_t cap = 0, stride = 0, psl = 0, share_len = 0, ext_stride = 0;
+  size_t tab_off = 0, meta_off = 0, rows_off = 0, out_off = 0, out_bytes = 0, bytes = 0;
+};
+struct UploadOut {  // byte offsets within the output block of a group of n reports
+  size_t fields, times, ids, ext_len, hct_len, pub, shares, ext, hcfg, lcfg, status, bytes;
+};
+void upload_out_layout(const UploadLayout& L, uint32_t n, UploadOut* O);
+// bytes of staging one report takes (inputs and outputs, without the per-array rounding)
+size_t upload_report_bytes(const UploadJob* j);
+void upload_layout(const UploadJob* j, uint32_t cap, UploadLayout* L);
+// the AEAD kernel an upload through opener o takes on engine e (option upload_aead resolved):
+// true = k_aead_open_wide
+bool upload_job_wide(prio3_engine* e, const janus_hpke_opener* o);
+// a group's staging target (prio3_runtime.hip: STAGING_TARGET); a job whose rows exceed it runs
+// the batch form
+constexpr size_t UPLOAD_STAGING_BYTES = (size_t)96 << 20;
+// equal keys may share one launch chain: the VDAF instance (engine_group_key), both openers and
+// config IDs, the strides and the AEAD kernel choice
+uint64_t upload_group_key(const UploadJob* j);
+struct UploadRun {
+  int device = 0;
+  hipStream_t st = nullptr;
+  Slab* slab = nullptr;
+  prio3_engine* lead = nullptr;
+};
+// the group's inputs into a device area (two DMAs), the chain once, the output block back into the
+// staging (one DMA); on success the caller synchronises r->st, releases r->slab and returns the
+// stream (ws_exec_stream_put)
+int upload_group_issue(const UploadJob& proto, const UploadLayout& L, uint8_t* stg, uint32_t n,
+                       uint32_t njobs, UploadRun* r, bool own_queue);
+void upload_group_collect(prio3_engine* lead);  // folds finished timing events into the engine
+int exec_upload(UploadJob* job);
+uint64_t exec_upload_load(int exec_id);  // reports of the upload jobs begun and not completed
+
 // ---- tickets (the *_submit entry points of janus_prio3.h) ---------------------------------
 // The two halves of exec_submit / exec_leader / exec_leader_next (Exec::begin / done / complete of
 // prio3_exec.h).  begin copies *job, stages its inputs on the calling thread and returns; every
@@ -515,6 +593,7 @@ struct ExecTicket;
 int exec_submit_begin(const ExecJob* job, int notify_fd, ExecTicket** out);
 int exec_leader_begin(const LeaderJob* job, int notify_fd, ExecTicket** out);
 int exec_leader_next_begin(const LNextJob* job, int notify_fd, ExecTicket** out);
+int exec_upload_begin(const UploadJob* job, int notify_fd, ExecTicket** out);
 bool exec_ticket_done(const ExecTicket* t);
 int exec_ticket_complete(ExecTicket* t, void* job_out);
 // the sealer's GPU and its KEM's Nenc (prio3_client_prepare_reports_device)

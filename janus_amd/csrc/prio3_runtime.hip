@@ -599,8 +599,9 @@ void host_cpu_add(int kind, double stage_ns, double unstage_ns) {
   static std::once_flag once;
   std::call_once(once, [] {
     std::atexit([] {
-      static const char* names[] = {"prepare", "accumulate", "leader", "leader_next", "hpke"};
-      for (int k = 0; k < 5; k++)
+      static const char* names[] = {"prepare", "accumulate", "leader", "leader_next", "hpke",
+                                    "upload"};
+      for (int k = 0; k < 6; k++)
         if (const uint64_t n = g_host_cpu[k][2])
           fprintf(stderr, "janus host cpu: %s jobs %lu stage %.3f s unstage %.3f s (%.1f / %.1f us per job)\n",
                   names[k], (unsigned long)n, g_host_cpu[k][0] / 1e9, g_host_cpu[k][1] / 1e9,
@@ -1160,6 +1161,113 @@ struct HpkePolicy {
   }
 };
 
+// ---- leader upload groups ----
+struct UploadPolicy {
+  static constexpr int kind = 5;
+  typedef UploadJob Job;
+  // the chain's HPKE stage is the open's long dependent chain (HpkePolicy): the light-load
+  // pipeline's concurrent groups at every load
+  static uint64_t heavy_default() { return UINT64_MAX / 4; }
+  struct State {
+    UploadJob proto;  // the group's lead engine, openers and strides
+    uint32_t n = 0, cap = 0, jobs = 0;
+    UploadLayout L;
+  };
+  typedef UploadRun Handle;
+  static uint64_t key(Job* j) { return upload_group_key(j); }
+  static uint32_t reports(const State& s) { return s.n; }
+  static bool create(State& s, Job* j, size_t* bytes) {
+    s.proto = *j;
+    const size_t per = upload_report_bytes(j);
+    const uint32_t cap_b = (uint32_t)std::max<size_t>(1, (STAGING_TARGET - ((size_t)1 << 20)) / per);
+    s.cap = std::max(j->n, std::min(UPLOAD_MAX_GROUP, cap_b));
+    if (s.cap > UPLOAD_MAX_GROUP) return false;
+    upload_layout(j, s.cap, &s.L);
+    *bytes = s.L.bytes;
+    return true;
+  }
+  static bool reserve(State& s, Job* j) {
+    if (s.jobs >= UPLOAD_MAX_JOBS || s.n + j->n > s.cap) return false;
+    j->c0 = s.n;
+    j->slot = s.jobs++;
+    s.n += j->n;
+    return true;
+  }
+  static void stage(State& s, Staging& g, Job* j) {
+    const UploadLayout& L = s.L;
+    if (j->c0 == 0) memset(g.p, 0, 256);  // the head: the list counters the group's DMA delivers
+    UploadJobRow row;
+    for (int i = 0; i < 8; i++) {  // BE words, as the kernels' AAD takes them
+      const uint8_t* b = j->task_id + 4 * i;
+      row.task[i] = (uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3];
+    }
+    row.now = j->now;
+    row.deadline = j->deadline;
+    row.task_exp = j->task_exp;
+    row.expiry_age = j->expiry_age;
+    memcpy(g.p + L.tab_off + sizeof(UploadJobRow) * (size_t)j->slot, &row, sizeof row);
+    UploadMeta* m = (UploadMeta*)(g.p + L.meta_off) + j->c0;
+    for (uint32_t i = 0; i < j->n; i++) m[i] = UploadMeta{j->report_len[i], (uint16_t)j->slot, 0};
+    stream_copy(g.p + L.rows_off + (size_t)L.stride * j->c0, j->reports, (size_t)L.stride * j->n);
+  }
+  static int issue(int device, State& s, Staging& g, Handle* h, bool own_queue) {
+    (void)device;
+    return upload_group_issue(s.proto, s.L, g.p, s.n, s.jobs, h, own_queue);
+  }
+  static bool prepared(const Handle& h) { return done(h); }
+  static bool done(const Handle& h) { return hipStreamQuery(h.st) != hipErrorNotReady; }
+  static int finish(Handle* h) {
+    const hipError_t q = hipStreamSynchronize(h->st);
+    upload_group_collect(h->lead);
+    ws_release(h->slab, h->st);
+    ws_exec_stream_put(h->device, h->st);
+    return q == hipSuccess ? PRIO3_OK : PRIO3_EDEVICE;
+  }
+  // The job's columns of the output block, and the helper's ciphertext rows cut out of the job's
+  // own staged Report rows (they never crossed the link): a report with status 0 whose helper
+  // `enc` has helper_enc_len bytes and whose payload fits helper_ct_stride gets both rows, every
+  // other report zeros -- what k_rep_decode and k_up_finish leave in the batch form.
+  static void unstage(State& s, Staging& g, Job* j) {
+    const UploadLayout& L = s.L;
+    UploadOut O;
+    upload_out_layout(L, s.n, &O);
+    const uint8_t* o = g.p + L.out_off;
+    const size_t c0 = j->c0, n = j->n;
+    memcpy(j->ids, o + O.ids + 16 * c0, 16 * n);
+    memcpy(j->times, o + O.times + 8 * c0, 8 * n);
+    if (L.psl) memcpy(j->pub, o + O.pub + (size_t)L.psl * c0, (size_t)L.psl * n);
+    memcpy(j->shares, o + O.shares + (size_t)L.share_len * c0, (size_t)L.share_len * n);
+    if (L.ext_stride)
+      memcpy(j->ext, o + O.ext + (size_t)L.ext_stride * c0, (size_t)L.ext_stride * n);
+    memcpy(j->ext_len, o + O.ext_len + 4 * c0, 4 * n);
+    memcpy(j->hct_len, o + O.hct_len + 4 * c0, 4 * n);
+    memcpy(j->hcfg, o + O.hcfg + c0, n);
+    memcpy(j->lcfg, o + O.lcfg + c0, n);
+    memcpy(j->status, o + O.status + c0, n);
+    const uint32_t* fields = (const uint32_t*)(o + O.fields) + 10 * c0;  // JANUS_DAP_REPORT_FIELDS
+    const uint8_t* status = o + O.status + c0;
+    const uint8_t* rows = g.p + L.rows_off + (size_t)L.stride * c0;
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t* f = fields + 10 * i;
+      const uint8_t* row = rows + (size_t)L.stride * i;
+      const bool hok = status[i] == 0 && f[7] == j->henc_len && f[9] <= j->hct_stride;
+      if (j->henc_len) {
+        uint8_t* d = j->henc + (size_t)j->henc_len * i;
+        if (hok)
+          memcpy(d, row + f[6], j->henc_len);
+        else
+          memset(d, 0, j->henc_len);
+      }
+      if (j->hct_stride) {
+        uint8_t* d = j->hct + (size_t)j->hct_stride * i;
+        const uint32_t k = hok ? f[9] : 0u;
+        if (k) memcpy(d, row + f[8], k);
+        memset(d + k, 0, j->hct_stride - k);
+      }
+    }
+  }
+};
+
 constexpr int N_EXEC = MAX_DEVICES * EXEC_LANES;
 
 template <class P>
@@ -1176,6 +1284,7 @@ Exec<AccPolicy>* g_acc = make_execs<AccPolicy>();
 Exec<LeaderPolicy>* g_lead = make_execs<LeaderPolicy>();
 Exec<LNextPolicy>* g_lnext = make_execs<LNextPolicy>();
 Exec<HpkePolicy>* g_hpke = make_execs<HpkePolicy>();
+Exec<UploadPolicy>* g_upload = make_execs<UploadPolicy>();
 
 bool exec_id_ok(int id) { return id >= 0 && id < N_EXEC; }
 
@@ -1223,6 +1332,12 @@ int exec_leader_next(LNextJob* job) {
   return g_lnext[job->device * EXEC_LANES].submit(job);
 }
 
+int exec_upload(UploadJob* job) {
+  const int id = engine_exec_id(job->e);
+  if (!exec_id_ok(id)) return PRIO3_EINVAL;
+  return g_upload[id].submit(job);
+}
+
 // ---- tickets ----
 struct ExecTicket {
   int kind = 0, id = 0;
@@ -1259,8 +1374,16 @@ int exec_leader_next_begin(const LNextJob* job, int notify_fd, ExecTicket** out)
   return ticket_begin(g_lnext, EXEC_LNEXT, job->device * EXEC_LANES, job, notify_fd, out);
 }
 
+int exec_upload_begin(const UploadJob* job, int notify_fd, ExecTicket** out) {
+  *out = nullptr;
+  const int id = engine_exec_id(job->e);
+  if (!exec_id_ok(id)) return PRIO3_EINVAL;
+  return ticket_begin(g_upload, EXEC_UPLOAD, id, job, notify_fd, out);
+}
+
 bool exec_ticket_done(const ExecTicket* x) {
   switch (x->kind) {
+    case EXEC_UPLOAD: return g_upload[x->id].done((const Exec<UploadPolicy>::Ticket*)x->t);
     case EXEC_PREP: return g_prep[x->id].done((const Exec<PrepPolicy>::Ticket*)x->t);
     case EXEC_LEADER: return g_lead[x->id].done((const Exec<LeaderPolicy>::Ticket*)x->t);
     default: return g_lnext[x->id].done((const Exec<LNextPolicy>::Ticket*)x->t);
@@ -1275,6 +1398,9 @@ int exec_ticket_complete(ExecTicket* x, void* job_out) {
       break;
     case EXEC_LEADER:
       rc = g_lead[x->id].complete((Exec<LeaderPolicy>::Ticket*)x->t, (LeaderJob*)job_out);
+      break;
+    case EXEC_UPLOAD:
+      rc = g_upload[x->id].complete((Exec<UploadPolicy>::Ticket*)x->t, (UploadJob*)job_out);
       break;
     default:
       rc = g_lnext[x->id].complete((Exec<LNextPolicy>::Ticket*)x->t, (LNextJob*)job_out);
@@ -1338,6 +1464,7 @@ int exec_stats(int kind, int id, ExecStats* out) {
     case EXEC_LEADER: *out = g_lead[id].get_stats(); return PRIO3_OK;
     case EXEC_LNEXT: *out = g_lnext[id].get_stats(); return PRIO3_OK;
     case EXEC_HPKE: *out = g_hpke[id].get_stats(); return PRIO3_OK;
+    case EXEC_UPLOAD: *out = g_upload[id].get_stats(); return PRIO3_OK;
     default: return PRIO3_EINVAL;
   }
 }
@@ -1350,6 +1477,7 @@ int exec_control(int kind, int id, const char* key, int64_t value) {
     case EXEC_LEADER: return g_lead[id].control(key, value);
     case EXEC_LNEXT: return g_lnext[id].control(key, value);
     case EXEC_HPKE: return g_hpke[id].control(key, value);
+    case EXEC_UPLOAD: return g_upload[id].control(key, value);
     default: return PRIO3_EINVAL;
   }
 }
@@ -1357,6 +1485,11 @@ int exec_control(int kind, int id, const char* key, int64_t value) {
 uint64_t exec_load(int id) {
   if (!exec_id_ok(id)) return 0;
   return g_prep[id].get_stats().active_reports + g_lead[id].get_stats().active_reports;
+}
+
+uint64_t exec_upload_load(int id) {
+  if (!exec_id_ok(id)) return 0;
+  return g_upload[id].get_stats().active_reports;
 }
 
 // ---- tracing -------------------------------------------------------------------------------

@@ -38,6 +38,22 @@
 //    T = ceil(N / G) blocks.  A short last block is masked before it is hashed and stored.
 //  - A failed tag (or KEM) zeroes the plaintext row, sets DecryptFailure and, when the global
 //    keypair has the same config ID, puts the report on the global opener's list.
+//
+// The group form (prio3_leader_upload_job: the upload executor's coalesced group, prio3_runtime.h)
+// runs the same chain once for the jobs of many tasks.  What differs between the jobs -- task ID,
+// now, deadline, task expiration, expiry age -- sits in the group's job table, and each report
+// carries its length and its job's slot (UploadMeta).  The kernels that read one of those are
+// templates over TAB: the one-task instantiations (TAB = false) are the code above, the group's
+// take the task-ID words and the times from the report's own job row.
+//   k_up_front    k_rep_decode and k_up_pre in one launch, one wave per report: the walk over the
+//                 prefixes, the small outputs, then the checks on the values still in registers
+//                 (lane 0 stores the verdict); one list atomic per workgroup and list.  It writes
+//                 no helper rows: the job form cuts them out of its staged input on the host.  The
+//                 list counters arrive as zeros with the group's first DMA (no memset).
+//   then per opener k_up_gather<true>, k_hpke_open / k_hpke_keys (group-uniform: the openers are in
+//   the group key), k_up_post1 or k_aead_open_wide<NR, true> (the four reports of a wave may belong
+//   to four jobs: each 16-lane row reads its own job's task ID), and k_up_finish<true>.
+//   One opener: 5 launches (7 in the one-task form, the counter memset included); two: 8 (10).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +63,7 @@
 #include "../../include/janus_dap.h"
 #include "../../include/janus_hpke.h"
 #include "../../include/janus_prio3.h"
+#include "dap_report.h"
 #include "prio3_host.h"
 #include "aes_device.h"
 #include "ghash_device.h"
@@ -77,7 +94,18 @@ struct UpArgs {
   // outputs
   uint8_t *pub, *shares, *ext;
   uint32_t* ext_len;
+  // the group form (TAB instantiations): per report its length and job slot, the job table
+  const UploadMeta* meta;
+  const UploadJobRow* jtab;
 };
+// word i of the task ID in report r's AAD: the launch's (one task) or its job's (TAB)
+template <bool TAB>
+DEV uint32_t task_word(const UpArgs& a, uint32_t r, uint32_t i) {
+  if constexpr (TAB)
+    return a.jtab[a.meta[r].slot].task[i];
+  else
+    return a.task[i];
+}
 
 // bytes [off, off + 16) of a 4-byte aligned row as LE words; no dword that starts at or past `end`
 // is loaded (it reads as zero), so nothing past the field's last dword is touched
@@ -149,7 +177,96 @@ __global__ __launch_bounds__(256) void k_up_pre(UpArgs a) {
   }
 }
 
+// The group form's front: k_rep_decode and k_up_pre over the reports of a coalesced group, one
+// wave per report.  Every lane walks the prefixes (wave-uniform addresses, as in k_rep_decode), the
+// lanes share the small outputs, and the checks of k_up_pre run on the time and config ID still in
+// registers against the report's job row; lane 0 stores the verdict.  The four waves of a workgroup
+// share one atomic per list.
+__global__ __launch_bounds__(256) void k_up_front(UpArgs a) {
+  __shared__ int s_pass[4];
+  __shared__ uint32_t s_at[4];
+  const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * 4 + w;
+  int pass = -1;
+  if (r < a.n) {
+    const uint8_t* row = a.rows + (size_t)a.stride * r;
+    const UploadMeta m = a.meta[r];
+    uint32_t f[JANUS_DAP_REPORT_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, cfg[2] = {0, 0};
+    const bool ok = m.len <= a.stride && rep_parse(row, m.len, f, cfg);
+    if (!ok) {
+#pragma unroll
+      for (int i = 0; i < JANUS_DAP_REPORT_FIELDS; i++) f[i] = 0;
+      cfg[0] = cfg[1] = 0;
+    }
+    const bool hok = ok && f[7] == a.henc_len && f[9] <= a.hct_stride;
+    uint64_t t = 0;
+    if (ok)
+      for (int i = 0; i < 8; i++) t = (t << 8) | row[16 + i];
+    if (l < 16) a.ids[16 * (size_t)r + l] = ok ? row[l] : (uint8_t)0;
+    if (l == 16) a.times[r] = t;
+    if (l == 17) {
+#pragma unroll
+      for (int i = 0; i < JANUS_DAP_REPORT_FIELDS; i++)
+        a.fields[(size_t)JANUS_DAP_REPORT_FIELDS * r + i] = f[i];
+    }
+    if (l == 18) {
+      a.lcfg[r] = (uint8_t)cfg[0];
+      a.hcfg[r] = (uint8_t)cfg[1];
+      a.hct_len[r] = hok ? f[9] : 0u;
+    }
+    const UploadJobRow* jr = a.jtab + m.slot;
+    uint32_t st = 0, sel = 0;
+    if (!ok) {
+      st = PRIO3_UPLOAD_MALFORMED;
+    } else {
+      const bool mt = a.has[0] && cfg[0] == a.cfg[0], mg = a.has[1] && cfg[0] == a.cfg[1];
+      const bool et = mt && f[F_LENC_LEN] == a.nenc[0], eg = mg && f[F_LENC_LEN] == a.nenc[1];
+      const uint64_t age = jr->expiry_age;
+      if (t > jr->deadline)
+        st = PRIO3_UPLOAD_TOO_EARLY;
+      else if (t > jr->task_exp)  // UINT64_MAX: no expiration
+        st = PRIO3_UPLOAD_TASK_EXPIRED;
+      else if (age != ~0ull && t + age < t)
+        st = PRIO3_UPLOAD_HOST;  // Time::add overflows: the reference's internal error
+      else if (age != ~0ull && jr->now > t + age)
+        st = PRIO3_UPLOAD_EXPIRED;
+      else if (f[F_PUB_LEN] != a.psl)
+        st = PRIO3_UPLOAD_DECODE_FAILURE;
+      else if (!mt && !mg)
+        st = PRIO3_UPLOAD_OUTDATED_HPKE_CONFIG;
+      else if (f[F_LPAY_LEN] < 16 || (!et && !eg))
+        st = PRIO3_UPLOAD_DECRYPT_FAILURE;
+      else {
+        pass = et ? 0 : 1;
+        sel = et && eg ? 2u : 0u;  // the task open's failure goes on to the global keypair
+      }
+    }
+    if (l == 0) {
+      a.status[r] = (uint8_t)st;
+      a.sel[r] = (uint8_t)sel;
+    }
+  }
+  if (l == 0) s_pass[w] = pass;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t c0 = 0, c1 = 0;
+    for (int i = 0; i < 4; i++) {
+      if (s_pass[i] == 0) s_at[i] = c0++;
+      if (s_pass[i] == 1) s_at[i] = c1++;
+    }
+    const uint32_t b0 = c0 ? atomicAdd(a.cnt, c0) : 0u;
+    const uint32_t b1 = c1 ? atomicAdd(a.cnt + 1, c1) : 0u;
+    for (int i = 0; i < 4; i++) {
+      if (s_pass[i] == 0) s_at[i] += b0;
+      if (s_pass[i] == 1) s_at[i] += b1;
+    }
+  }
+  __syncthreads();
+  if (l == 0 && pass >= 0) a.list[pass][s_at[w]] = r;
+}
+
 // one wave per listed report: enc into [nenc] rows; one-lane AEAD: payload and AAD rows too
+template <bool TAB>
 __global__ __launch_bounds__(256) void k_up_gather(UpArgs a, int pass, int one_lane) {
   const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63u;
   if (q >= min(a.cnt[pass], a.n)) return;
@@ -170,7 +287,9 @@ __global__ __launch_bounds__(256) void k_up_gather(UpArgs a, int pass, int one_l
   const uint32_t al = 60 + a.psl;
   uint8_t* aad = a.aad + (size_t)a.aad_stride * r;
   for (uint32_t k = l; k < a.aad_stride; k += 64)
-    aad[k] = k < 32 ? (uint8_t)(a.task[k >> 2] >> (8 * (3 - (k & 3)))) : k < al ? row[k - 32] : (uint8_t)0;
+    aad[k] = k < 32    ? (uint8_t)(task_word<TAB>(a, r, k >> 2) >> (8 * (3 - (k & 3))))
+             : k < al ? row[k - 32]
+                      : (uint8_t)0;
   if (l == 0) {
     a.ct_len[r] = pl;
     a.aad_len[r] = al;
@@ -207,7 +326,7 @@ DEV void gf_fold(uint32_t z[4], const uint32_t Hk[4], bool bit) {
   }
 }
 
-template <int NR>
+template <int NR, bool TAB>
 __global__ __launch_bounds__(256) void k_aead_open_wide(UpArgs a, int pass) {
   const uint32_t lim = min(a.cnt[pass], a.n);
   if (blockIdx.x * (256 / UP_G) >= lim) return;
@@ -268,7 +387,12 @@ __global__ __launch_bounds__(256) void k_aead_open_wide(UpArgs a, int pass) {
     if (s < na) {  // an AAD block: task ID (two blocks), then the row's first hdr bytes
       if (s < 2) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = s ? a.task[4 + i] : a.task[i];
+        for (int i = 0; i < 4; i++) {
+          if constexpr (TAB)  // the 16-lane row's own job
+            x[i] = task_word<true>(a, r, 4 * s + i);
+          else
+            x[i] = s ? a.task[4 + i] : a.task[i];
+        }
       } else {
         const uint32_t off = 16 * (s - 2);
         uint32_t w[4];
@@ -332,7 +456,9 @@ __global__ __launch_bounds__(256) void k_aead_open_wide(UpArgs a, int pass) {
 
 DEV uint32_t pt_be16(const uint8_t* p, uint32_t o) { return (uint32_t)p[o] << 8 | p[o + 1]; }
 
-// one wave per report: the plaintext's decode and checks, then every output row
+// one wave per report: the plaintext's decode and checks, then every output row (TAB: but the
+// helper's rows, which the group form does not make on the device)
+template <bool TAB>
 __global__ __launch_bounds__(256) void k_up_finish(UpArgs a) {
   const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63u;
   if (r >= a.n) return;
@@ -396,8 +522,10 @@ __global__ __launch_bounds__(256) void k_up_finish(UpArgs a) {
   }
   if (!ok) {
     if (l < 16) a.ids[16 * (size_t)r + l] = 0;
-    for (uint32_t k = l; k < a.henc_len; k += 64) a.henc[(size_t)a.henc_len * r + k] = 0;
-    for (uint32_t k = l; k < a.hct_stride; k += 64) a.hct[(size_t)a.hct_stride * r + k] = 0;
+    if constexpr (!TAB) {
+      for (uint32_t k = l; k < a.henc_len; k += 64) a.henc[(size_t)a.henc_len * r + k] = 0;
+      for (uint32_t k = l; k < a.hct_stride; k += 64) a.hct[(size_t)a.hct_stride * r + k] = 0;
+    }
     for (uint32_t k = l; 16 * k < ptl; k += 64) *(uint4*)(pp + 16 * k) = make_uint4(0, 0, 0, 0);
   }
   for (uint32_t k = l; k < a.psl; k += 64) a.pub[(size_t)a.psl * r + k] = ok ? row[28 + k] : (uint8_t)0;
@@ -417,6 +545,196 @@ __global__ __launch_bounds__(256) void k_up_finish(UpArgs a) {
 }
 
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the engine's option upload_aead (one lock per call)
+int upload_aead_option(prio3_engine* e) {
+  std::lock_guard<std::mutex> lk(e->mu);
+  return e->upload_aead;
+}
+// the AEAD kernel an upload through opener o takes on engine e under option value opt:
+// k_aead_open_wide or the one-lane body
+bool upload_wide(const prio3_engine* e, const janus_hpke_opener* o, int opt) {
+  const uint32_t expect = 6 + e->sz.leader_input_share_len + 16;  // a report without extensions
+  return hpke_opener_aead(o) != JANUS_HPKE_AEAD_CHACHA20_POLY1305 &&
+         (opt == 2 || (opt == 0 && expect >= UP_WIDE_MIN_PAYLOAD));
+}
+
+// One run of the chain: validated arguments, device buffers.
+struct UpCall {
+  janus_hpke_opener* op[2];  // the task's opener, the global one
+  uint8_t cfg[2];
+  uint32_t n, stride, ext_stride, henc_len, hct_stride;
+  const uint8_t* rows;
+  // outputs [n]...
+  uint8_t *ids, *pub, *shares, *ext, *hcfg, *lcfg, *status;
+  uint64_t* times;
+  uint32_t *ext_len, *hct_len;
+  // the one-task form: the launch's task and times, the row lengths, the helper's rows
+  const uint8_t* task_id;
+  uint64_t now, deadline, task_exp, expiry_age;
+  const uint32_t* len;
+  uint8_t *henc, *hct;
+  // the group form (meta != nullptr; at most UPLOAD_MAX_GROUP reports): the staged meta and job
+  // table, the list counters the group's DMA zeroed, the field table in the output block, the
+  // AEAD choice of the group's key
+  const UploadMeta* meta;
+  const UploadJobRow* jtab;
+  uint32_t *cnt, *fields;
+  bool wide[2];
+};
+
+// The per-opener launches and k_up_finish over the m reports of a.
+template <bool TAB>
+int upload_open_finish(prio3_engine* e, UpArgs& a, janus_hpke_opener* const op[2],
+                       const bool wide[2], uint32_t m, hipStream_t st) {
+  for (int p = 0; p < 2; p++) {
+    if (!op[p]) continue;
+    TIMED(e, st, "k_up_gather", (k_up_gather<TAB><<<(m + 3) / 4, 256, 0, st>>>(a, p, !wide[p])));
+    int hrc = PRIO3_OK;
+    if (wide[p]) {
+      TIMED(e, st, "k_hpke_keys",
+            hrc = hpke_upload_keys_launch(op[p], m, a.enc, a.keys, a.list[p], a.cnt + p, st));
+      if (hrc != PRIO3_OK) return hrc;
+      const uint32_t blocks = (m + 256 / UP_G - 1) / (256 / UP_G);
+      if (hpke_opener_aead(op[p]) == JANUS_HPKE_AEAD_AES_256_GCM)
+        TIMED(e, st, "k_aead_open_wide",
+              (k_aead_open_wide<14, TAB><<<blocks, 256, 0, st>>>(a, p)));
+      else
+        TIMED(e, st, "k_aead_open_wide",
+              (k_aead_open_wide<10, TAB><<<blocks, 256, 0, st>>>(a, p)));
+    } else {
+      TIMED(e, st, "k_hpke_open",
+            hrc = hpke_upload_open_launch(op[p], m, a.enc, a.ct, a.ct_len, a.pt_stride, a.aad,
+                                          a.aad_len, a.aad_stride, a.pt, a.hst, a.list[p],
+                                          a.cnt + p, st));
+      if (hrc != PRIO3_OK) return hrc;
+      TIMED(e, st, "k_up_post1", (k_up_post1<<<(m + 255) / 256, 256, 0, st>>>(a, p)));
+    }
+  }
+  TIMED(e, st, "k_up_finish", (k_up_finish<TAB><<<(m + 3) / 4, 256, 0, st>>>(a)));
+  return PRIO3_OK;
+}
+
+// The chain of call c on e's device (current) and stream st, in chunks of at most 65536 reports --
+// fewer when the pool cannot give a whole chunk's scratch -- for both forms.
+int upload_chain(prio3_engine* e, const UpCall& c, hipStream_t st) {
+  const bool grp = c.meta != nullptr;
+  const uint32_t n = c.n;
+  if (grp && n > UPLOAD_MAX_GROUP) return PRIO3_EINVAL;
+  const uint32_t psl = e->sz.public_share_len, L = e->sz.leader_input_share_len;
+  UpArgs a{};
+  a.stride = c.stride;
+  a.psl = psl;
+  a.share_len = L;
+  a.blind_len = e->sz.joint_rand_len ? e->sz.prep_msg_len : 0;
+  a.es = e->sz.field_bytes;
+  a.ext_stride = c.ext_stride;
+  a.pt_stride = (c.stride + 15) & ~15u;
+  a.aad_stride = (60 + psl + 15) & ~15u;
+  a.henc_len = c.henc_len;
+  a.hct_stride = c.hct_stride;
+  a.now = c.now;
+  a.deadline = c.deadline;
+  a.task_exp = c.task_exp;
+  a.expiry_age = c.expiry_age;
+  uint32_t encmax = 0;
+  bool wide[2] = {false, false}, any_one = false;
+  const int opt = grp ? 0 : upload_aead_option(e);
+  for (int p = 0; p < 2; p++) {
+    if (!c.op[p]) continue;
+    a.has[p] = 1;
+    a.cfg[p] = c.cfg[p];
+    a.nenc[p] = (uint32_t)hpke_opener_nenc(c.op[p]);
+    encmax = std::max(encmax, a.nenc[p]);
+    wide[p] = grp ? c.wide[p] : upload_wide(e, c.op[p], opt);
+    any_one = any_one || !wide[p];
+  }
+  for (int i = 0; c.task_id && i < 8; i++)
+    a.task[i] = (uint32_t)c.task_id[4 * i] << 24 | (uint32_t)c.task_id[4 * i + 1] << 16 |
+                (uint32_t)c.task_id[4 * i + 2] << 8 | c.task_id[4 * i + 3];
+  a.jtab = c.jtab;
+  // per-report scratch, each array 256-byte aligned: fields and malformed (the one-task form: the
+  // group's fields are in its output block and its front keeps no malformed byte), sel, keys, enc,
+  // plaintext, two lists; the one-lane AEAD's payload, AAD, lengths and status rows
+  const size_t rows[12] = {grp ? 0u : 4u * JANUS_DAP_REPORT_FIELDS, grp ? 0u : 1u, 1, 48,
+                           (encmax + 15) & ~15u, a.pt_stride, 4, 4,
+                           any_one ? a.pt_stride : 0u, any_one ? a.aad_stride : 0u,
+                           any_one ? 8u : 0u, any_one ? 1u : 0u};
+  size_t per = 0;
+  for (size_t b : rows) per += b;
+  size_t chunk = std::min<size_t>(((size_t)n + 63) & ~(size_t)63, 65536);
+  int rc = PRIO3_OK;
+  Slab* slab = nullptr;
+  for (;;) {  // all of a chunk's scratch or a smaller chunk
+    slab = ws_acquire(e->device, per * chunk + 14 * 256, st, &rc);
+    if (slab || chunk <= 64) break;
+    chunk = std::max<size_t>(64, (chunk / 2) & ~(size_t)63);
+  }
+  if (!slab) return rc;
+  uint8_t* arr[12];
+  {
+    uint8_t* b = slab->base + 256;  // the two list counters first
+    for (int i = 0; i < 12; i++) {
+      arr[i] = b;
+      b += up256(rows[i] * chunk);
+    }
+  }
+  a.cnt = grp ? c.cnt : (uint32_t*)slab->base;
+  a.bad = arr[1];
+  a.sel = arr[2];
+  a.keys = (uint32_t*)arr[3];
+  a.enc = arr[4];
+  a.pt = arr[5];
+  a.list[0] = (uint32_t*)arr[6];
+  a.list[1] = (uint32_t*)arr[7];
+  a.ct = arr[8];
+  a.aad = arr[9];
+  a.ct_len = (uint32_t*)arr[10];
+  a.aad_len = a.ct_len + chunk;
+  a.hst = arr[11];
+  auto body = [&]() -> int {
+    for (uint64_t off = 0; off < n; off += chunk) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
+      a.n = m;
+      a.rows = c.rows + (size_t)c.stride * off;
+      a.ids = c.ids + 16 * off;
+      a.times = c.times + off;
+      a.lcfg = c.lcfg + off;
+      a.hcfg = c.hcfg + off;
+      a.henc = c.henc ? c.henc + (size_t)c.henc_len * off : nullptr;
+      a.hct = c.hct ? c.hct + (size_t)c.hct_stride * off : nullptr;
+      a.hct_len = c.hct_len + off;
+      a.status = c.status + off;
+      a.pub = c.pub ? c.pub + (size_t)psl * off : nullptr;
+      a.shares = c.shares + (size_t)L * off;
+      a.ext = c.ext ? c.ext + (size_t)c.ext_stride * off : nullptr;
+      a.ext_len = c.ext_len + off;
+      // the counters: the group's first chunk finds them zeroed by its DMA
+      if (!grp || off) HIPCHK(hipMemsetAsync(a.cnt, 0, 8, st));
+      if (grp) {
+        a.meta = c.meta + off;
+        a.fields = c.fields + (size_t)JANUS_DAP_REPORT_FIELDS * off;
+        TIMED(e, st, "k_up_front", (k_up_front<<<(m + 3) / 4, 256, 0, st>>>(a)));
+      } else {
+        a.fields = (uint32_t*)arr[0];
+        int drc = 0;
+        TIMED(e, st, "k_rep_decode",
+              drc = janus_dap_report_decode_device(m, a.rows, c.stride, c.len + off, a.ids, a.times,
+                                                   a.fields, a.lcfg, a.hcfg, a.henc, c.henc_len,
+                                                   a.hct, a.hct_len, c.hct_stride, a.bad, st));
+        if (drc) return drc == JANUS_DAP_EDEVICE ? PRIO3_EDEVICE : PRIO3_EINVAL;
+        TIMED(e, st, "k_up_pre", (k_up_pre<<<(m + 255) / 256, 256, 0, st>>>(a)));
+      }
+      const int orc = grp ? upload_open_finish<true>(e, a, c.op, wide, m, st)
+                          : upload_open_finish<false>(e, a, c.op, wide, m, st);
+      if (orc != PRIO3_OK) return orc;
+    }
+    return PRIO3_OK;
+  };
+  rc = body();
+  ws_release(slab, st);
+  return rc;
+}
 
 }  // namespace
 
@@ -439,7 +757,7 @@ extern "C" int prio3_device_leader_upload(
   for (auto* o : op)
     if (o && hpke_opener_device(o) != e->device) return PRIO3_EINVAL;
   if (n == 0) return PRIO3_OK;
-  const uint32_t psl = e->sz.public_share_len, L = e->sz.leader_input_share_len;
+  const uint32_t psl = e->sz.public_share_len;
   if (!d_reports || !d_report_len || !d_report_ids || !d_times || !d_leader_input_shares ||
       !d_ext_len || !d_helper_config_ids || !d_helper_ct_len || !d_leader_config_ids || !d_status ||
       (psl && !d_public_shares) || (ext_stride && !d_extensions) ||
@@ -447,136 +765,36 @@ extern "C" int prio3_device_leader_upload(
     return PRIO3_EINVAL;
   DeviceGuard dg_(e->device);
   HIPCHK(dg_.rc);
-  hipStream_t st = (hipStream_t)stream;
-  int opt;
-  {
-    std::lock_guard<std::mutex> lk(e->mu);
-    opt = e->upload_aead;
-  }
-  UpArgs a{};
-  a.stride = report_stride;
-  a.psl = psl;
-  a.share_len = L;
-  a.blind_len = e->sz.joint_rand_len ? e->sz.prep_msg_len : 0;
-  a.es = e->sz.field_bytes;
-  a.ext_stride = ext_stride;
-  a.pt_stride = (report_stride + 15) & ~15u;
-  a.aad_stride = (60 + psl + 15) & ~15u;
-  a.henc_len = helper_enc_len;
-  a.hct_stride = helper_ct_stride;
-  a.now = now;
-  a.deadline = report_deadline;
-  a.task_exp = task_expiration;
-  a.expiry_age = report_expiry_age;
-  uint32_t encmax = 0;
-  bool wide[2] = {false, false}, any_one = false;
-  const uint32_t expect = 6 + L + 16;  // the payload of a report without extensions
-  for (int p = 0; p < 2; p++) {
-    if (!op[p]) continue;
-    a.has[p] = 1;
-    a.cfg[p] = p ? global_config_id : task_config_id;
-    a.nenc[p] = (uint32_t)hpke_opener_nenc(op[p]);
-    encmax = std::max(encmax, a.nenc[p]);
-    wide[p] = hpke_opener_aead(op[p]) != JANUS_HPKE_AEAD_CHACHA20_POLY1305 &&
-              (opt == 2 || (opt == 0 && expect >= UP_WIDE_MIN_PAYLOAD));
-    any_one = any_one || !wide[p];
-  }
-  for (int i = 0; i < 8; i++)
-    a.task[i] = (uint32_t)task_id[4 * i] << 24 | (uint32_t)task_id[4 * i + 1] << 16 |
-                (uint32_t)task_id[4 * i + 2] << 8 | task_id[4 * i + 3];
-  // per-report scratch, each array 256-byte aligned: fields, malformed, sel, keys, enc, plaintext,
-  // two lists; the one-lane AEAD's payload, AAD, lengths and status rows
-  const size_t rows[12] = {4 * JANUS_DAP_REPORT_FIELDS, 1, 1, 48, (encmax + 15) & ~15u, a.pt_stride,
-                           4, 4, any_one ? a.pt_stride : 0u, any_one ? a.aad_stride : 0u,
-                           any_one ? 8u : 0u, any_one ? 1u : 0u};
-  size_t per = 0;
-  for (size_t b : rows) per += b;
-  size_t chunk = std::min<size_t>(((size_t)n + 63) & ~(size_t)63, 65536);
-  int rc = PRIO3_OK;
-  Slab* slab = nullptr;
-  for (;;) {  // all of a chunk's scratch or a smaller chunk
-    slab = ws_acquire(e->device, per * chunk + 14 * 256, st, &rc);
-    if (slab || chunk <= 64) break;
-    chunk = std::max<size_t>(64, (chunk / 2) & ~(size_t)63);
-  }
-  if (!slab) return rc;
-  uint8_t* arr[12];
-  {
-    uint8_t* b = slab->base + 256;  // the two list counters first
-    for (int i = 0; i < 12; i++) {
-      arr[i] = b;
-      b += up256(rows[i] * chunk);
-    }
-  }
-  a.cnt = (uint32_t*)slab->base;
-  a.fields = (uint32_t*)arr[0];
-  a.bad = arr[1];
-  a.sel = arr[2];
-  a.keys = (uint32_t*)arr[3];
-  a.enc = arr[4];
-  a.pt = arr[5];
-  a.list[0] = (uint32_t*)arr[6];
-  a.list[1] = (uint32_t*)arr[7];
-  a.ct = arr[8];
-  a.aad = arr[9];
-  a.ct_len = (uint32_t*)arr[10];
-  a.aad_len = a.ct_len + chunk;
-  a.hst = arr[11];
-  auto body = [&]() -> int {
-    for (uint64_t off = 0; off < n; off += chunk) {
-      const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
-      a.n = m;
-      a.rows = d_reports + (size_t)report_stride * off;
-      a.ids = d_report_ids + 16 * off;
-      a.times = d_times + off;
-      a.lcfg = d_leader_config_ids + off;
-      a.hcfg = d_helper_config_ids + off;
-      a.henc = d_helper_enc ? d_helper_enc + (size_t)helper_enc_len * off : nullptr;
-      a.hct = d_helper_ct ? d_helper_ct + (size_t)helper_ct_stride * off : nullptr;
-      a.hct_len = d_helper_ct_len + off;
-      a.status = d_status + off;
-      a.pub = d_public_shares ? d_public_shares + (size_t)psl * off : nullptr;
-      a.shares = d_leader_input_shares + (size_t)L * off;
-      a.ext = d_extensions ? d_extensions + (size_t)ext_stride * off : nullptr;
-      a.ext_len = d_ext_len + off;
-      HIPCHK(hipMemsetAsync(a.cnt, 0, 8, st));
-      int drc = 0;
-      TIMED(e, st, "k_rep_decode",
-            drc = janus_dap_report_decode_device(m, a.rows, report_stride, d_report_len + off, a.ids,
-                                                 a.times, a.fields, a.lcfg, a.hcfg, a.henc,
-                                                 helper_enc_len, a.hct, a.hct_len, helper_ct_stride,
-                                                 a.bad, st));
-      if (drc) return drc == JANUS_DAP_EDEVICE ? PRIO3_EDEVICE : PRIO3_EINVAL;
-      TIMED(e, st, "k_up_pre", (k_up_pre<<<(m + 255) / 256, 256, 0, st>>>(a)));
-      for (int p = 0; p < 2; p++) {
-        if (!op[p]) continue;
-        TIMED(e, st, "k_up_gather", (k_up_gather<<<(m + 3) / 4, 256, 0, st>>>(a, p, !wide[p])));
-        int hrc = PRIO3_OK;
-        if (wide[p]) {
-          TIMED(e, st, "k_hpke_keys",
-                hrc = hpke_upload_keys_launch(op[p], m, a.enc, a.keys, a.list[p], a.cnt + p, st));
-          if (hrc != PRIO3_OK) return hrc;
-          const uint32_t blocks = (m + 256 / UP_G - 1) / (256 / UP_G);
-          if (hpke_opener_aead(op[p]) == JANUS_HPKE_AEAD_AES_256_GCM)
-            TIMED(e, st, "k_aead_open_wide", (k_aead_open_wide<14><<<blocks, 256, 0, st>>>(a, p)));
-          else
-            TIMED(e, st, "k_aead_open_wide", (k_aead_open_wide<10><<<blocks, 256, 0, st>>>(a, p)));
-        } else {
-          TIMED(e, st, "k_hpke_open",
-                hrc = hpke_upload_open_launch(op[p], m, a.enc, a.ct, a.ct_len, a.pt_stride, a.aad,
-                                              a.aad_len, a.aad_stride, a.pt, a.hst, a.list[p],
-                                              a.cnt + p, st));
-          if (hrc != PRIO3_OK) return hrc;
-          TIMED(e, st, "k_up_post1", (k_up_post1<<<(m + 255) / 256, 256, 0, st>>>(a, p)));
-        }
-      }
-      TIMED(e, st, "k_up_finish", (k_up_finish<<<(m + 3) / 4, 256, 0, st>>>(a)));
-    }
-    return PRIO3_OK;
-  };
-  rc = body();
-  ws_release(slab, st);
-  return rc;
+  UpCall c{};
+  c.op[0] = op[0];
+  c.op[1] = op[1];
+  c.cfg[0] = task_config_id;
+  c.cfg[1] = global_config_id;
+  c.n = n;
+  c.stride = report_stride;
+  c.ext_stride = ext_stride;
+  c.henc_len = helper_enc_len;
+  c.hct_stride = helper_ct_stride;
+  c.rows = d_reports;
+  c.ids = d_report_ids;
+  c.times = d_times;
+  c.pub = d_public_shares;
+  c.shares = d_leader_input_shares;
+  c.ext = d_extensions;
+  c.ext_len = d_ext_len;
+  c.hcfg = d_helper_config_ids;
+  c.hct_len = d_helper_ct_len;
+  c.lcfg = d_leader_config_ids;
+  c.status = d_status;
+  c.task_id = task_id;
+  c.now = now;
+  c.deadline = report_deadline;
+  c.task_exp = task_expiration;
+  c.expiry_age = report_expiry_age;
+  c.len = d_report_len;
+  c.henc = d_helper_enc;
+  c.hct = d_helper_ct;
+  return upload_chain(e, c, (hipStream_t)stream);
 }
 
 extern "C" int prio3_leader_upload_batch(
@@ -647,4 +865,145 @@ extern "C" int prio3_leader_upload_batch(
   }
   ws_stream_put(e->device, st);
   return rc;
+}
+
+// ---- the upload executor's hooks (prio3_runtime.h) ----
+bool upload_job_wide(prio3_engine* e, const janus_hpke_opener* o) {
+  return upload_wide(e, o, upload_aead_option(e));
+}
+
+size_t upload_report_bytes(const UploadJob* j) {
+  return (size_t)j->stride + sizeof(UploadMeta) + 4 * JANUS_DAP_REPORT_FIELDS + 8 + 16 + 4 + 4 +
+         (size_t)j->e->sz.public_share_len + j->e->sz.leader_input_share_len + j->ext_stride + 3;
+}
+
+void upload_out_layout(const UploadLayout& L, uint32_t n, UploadOut* O) {
+  size_t off = 0;
+  auto take = [&](size_t per) {
+    const size_t at = off;
+    off += up256(per * n);
+    return at;
+  };
+  O->fields = take(4 * JANUS_DAP_REPORT_FIELDS);
+  O->times = take(8);
+  O->ids = take(16);
+  O->ext_len = take(4);
+  O->hct_len = take(4);
+  O->pub = take(L.psl);
+  O->shares = take(L.share_len);
+  O->ext = take(L.ext_stride);
+  O->hcfg = take(1);
+  O->lcfg = take(1);
+  O->status = take(1);
+  O->bytes = off;
+}
+
+void upload_layout(const UploadJob* j, uint32_t cap, UploadLayout* L) {
+  L->cap = cap;
+  L->stride = j->stride;
+  L->psl = j->e->sz.public_share_len;
+  L->share_len = j->e->sz.leader_input_share_len;
+  L->ext_stride = j->ext_stride;
+  L->tab_off = 256;  // the head: the chain's list counters
+  L->meta_off = L->tab_off + up256(sizeof(UploadJobRow) * UPLOAD_MAX_JOBS);
+  L->rows_off = L->meta_off + up256(sizeof(UploadMeta) * (size_t)cap);
+  L->out_off = L->rows_off + up256((size_t)j->stride * cap);
+  UploadOut O;
+  upload_out_layout(*L, cap, &O);
+  L->out_bytes = O.bytes;
+  L->bytes = L->out_off + O.bytes;
+}
+
+uint64_t upload_group_key(const UploadJob* j) {
+  uint64_t h = engine_group_key(j->e);
+  auto mix = [&](uint64_t x) { h = (h ^ x) * 1099511628211ull; };
+  for (int p = 0; p < 2; p++) {
+    mix((uint64_t)(uintptr_t)j->op[p]);
+    mix(j->op[p] ? hpke_opener_key(j->op[p]) : 0);
+    mix(j->cfg[p]);
+    mix(j->wide[p]);
+  }
+  mix(j->stride);
+  mix(j->ext_stride);
+  mix(j->henc_len);
+  mix(j->hct_stride);
+  return h;
+}
+
+int upload_group_issue(const UploadJob& pj, const UploadLayout& L, uint8_t* stg, uint32_t n,
+                       uint32_t njobs, UploadRun* r, bool own_queue) {
+  prio3_engine* e = pj.e;
+  *r = UploadRun();
+  if (n == 0 || n > L.cap || njobs == 0 || njobs > UPLOAD_MAX_JOBS) return PRIO3_EINVAL;
+  DeviceGuard dg_(e->device);
+  HIPCHK(dg_.rc);
+  hipStream_t st = own_queue ? ws_exec_stream_get(e->device) : ws_stream_get(e->device);
+  if (!st) return PRIO3_EDEVICE;
+  UploadOut O;
+  upload_out_layout(L, n, &O);
+  // the device area: the staged head, table and meta as they lie in the staging, the rows, the
+  // output block
+  const size_t in_bytes = L.meta_off + sizeof(UploadMeta) * (size_t)n;
+  const size_t d_rows = up256(in_bytes), row_bytes = (size_t)L.stride * n;
+  const size_t d_out = d_rows + up256(row_bytes);
+  int rc = PRIO3_OK;
+  Slab* sl = ws_acquire(e->device, d_out + O.bytes, st, &rc);
+  if (!sl) {
+    ws_exec_stream_put(e->device, st);
+    return rc;
+  }
+  uint8_t* b = sl->base;
+  uint8_t* o = b + d_out;
+  if (hipMemcpyAsync(b, stg, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+      (row_bytes && hipMemcpyAsync(b + d_rows, stg + L.rows_off, row_bytes, hipMemcpyHostToDevice,
+                                   st) != hipSuccess))
+    rc = PRIO3_EDEVICE;
+  if (rc == PRIO3_OK) {
+    UpCall c{};
+    c.op[0] = pj.op[0];
+    c.op[1] = pj.op[1];
+    c.cfg[0] = pj.cfg[0];
+    c.cfg[1] = pj.cfg[1];
+    c.n = n;
+    c.stride = L.stride;
+    c.ext_stride = L.ext_stride;
+    c.henc_len = pj.henc_len;
+    c.hct_stride = pj.hct_stride;
+    c.rows = b + d_rows;
+    c.ids = o + O.ids;
+    c.times = (uint64_t*)(o + O.times);
+    c.pub = L.psl ? o + O.pub : nullptr;
+    c.shares = o + O.shares;
+    c.ext = L.ext_stride ? o + O.ext : nullptr;
+    c.ext_len = (uint32_t*)(o + O.ext_len);
+    c.hcfg = o + O.hcfg;
+    c.hct_len = (uint32_t*)(o + O.hct_len);
+    c.lcfg = o + O.lcfg;
+    c.status = o + O.status;
+    c.meta = (const UploadMeta*)(b + L.meta_off);
+    c.jtab = (const UploadJobRow*)(b + L.tab_off);
+    c.cnt = (uint32_t*)b;
+    c.fields = (uint32_t*)(o + O.fields);
+    c.wide[0] = pj.wide[0];
+    c.wide[1] = pj.wide[1];
+    rc = upload_chain(e, c, st);
+  }
+  if (rc == PRIO3_OK &&
+      hipMemcpyAsync(stg + L.out_off, o, O.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = PRIO3_EDEVICE;
+  if (rc != PRIO3_OK) {
+    (void)hipStreamSynchronize(st);
+    ws_release(sl, st);
+    ws_exec_stream_put(e->device, st);
+    return rc;
+  }
+  r->device = e->device;
+  r->st = st;
+  r->slab = sl;
+  r->lead = e;
+  return PRIO3_OK;
+}
+
+void upload_group_collect(prio3_engine* lead) {
+  if (lead && lead->timing) collect_times(lead, false);
 }

@@ -87,6 +87,7 @@ class Prio3ExecutorStats(C.Structure):
 
 #: executor kinds of prio3_executor_stats_get
 EXEC_PREPARE, EXEC_ACCUMULATE, EXEC_LEADER_INIT, EXEC_LEADER_NEXT = 0, 1, 2, 3
+EXEC_UPLOAD = 5  # the leader upload's (4 is the HPKE open's, janus_amd/hpke.py)
 
 
 class Prio3Sizes(C.Structure):
@@ -130,6 +131,32 @@ class Prio3HelperJobOut(C.Structure):
         "segment_ids", "segment_starts", "reject", "duplicate", "info", "prep_msgs", "status",
         "agg_shares", "counts", "checksums", "intervals")]
 
+
+#: the report limit of prio3_leader_upload_job's in-group path (PRIO3_UPLOAD_JOB_MAX_REPORTS); a
+#: larger job runs prio3_leader_upload_batch inside the entry point
+UPLOAD_JOB_MAX_REPORTS = 4096
+
+
+class Prio3UploadJobIn(C.Structure):
+    """prio3_upload_job_in (include/janus_prio3.h)."""
+    _fields_ = [("task_opener", C.c_void_p), ("global_opener", C.c_void_p),
+                ("task_config_id", C.c_uint8), ("global_config_id", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("n", C.c_uint32), ("task_id", C.c_uint8 * 32),
+                ("now", C.c_uint64), ("report_deadline", C.c_uint64),
+                ("task_expiration", C.c_uint64), ("report_expiry_age", C.c_uint64),
+                ("reports", C.c_void_p), ("report_len", C.c_void_p),
+                ("report_stride", C.c_uint32), ("ext_stride", C.c_uint32),
+                ("helper_enc_len", C.c_uint32), ("helper_ct_stride", C.c_uint32)]
+
+
+class Prio3UploadJobOut(C.Structure):
+    """prio3_upload_job_out (include/janus_prio3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "report_ids", "times", "public_shares", "leader_input_shares", "extensions", "ext_len",
+        "helper_config_ids", "helper_enc", "helper_ct", "helper_ct_len", "leader_config_ids",
+        "status")]
+
+
 class Prio3LeaderJobIn(C.Structure):
     """prio3_leader_job_in (include/janus_prio3.h)."""
     _fields_ = [("report_ids", C.c_void_p), ("times", C.c_void_p),
@@ -172,6 +199,7 @@ EXPORTED_SYMBOLS = (
     "prio3_helper_prepare_aggregate_batch_submit", "prio3_helper_aggregate_init_batch_ex_submit",
     "prio3_helper_aggregate_job_submit", "prio3_leader_prepare_init_batch_submit",
     "prio3_leader_finish_job_submit", "prio3_ticket_poll", "prio3_ticket_wait",
+    "prio3_leader_upload_job", "prio3_leader_upload_job_submit",
 )
 # include/janus_hpke.h (the batched HPKE opener, janus_amd/hpke.py)
 HPKE_EXPORTED_SYMBOLS = (
@@ -231,9 +259,11 @@ def load_library() -> C.CDLL:
                                                        vp, vp, vp, vp]
     L.prio3_helper_aggregate_job.argtypes = [vp, P(Prio3HelperJobIn), P(Prio3HelperJobOut)]
     L.prio3_leader_finish_job.argtypes = [vp, P(Prio3LeaderJobIn), P(Prio3LeaderJobOut)]
+    L.prio3_leader_upload_job.argtypes = [vp, P(Prio3UploadJobIn), P(Prio3UploadJobOut)]
     # the ticketed twins: the same arguments, then notify_fd and ticket_out
     for name in ("prio3_helper_prepare_aggregate_batch", "prio3_helper_aggregate_init_batch_ex",
-                 "prio3_helper_aggregate_job", "prio3_leader_finish_job"):
+                 "prio3_helper_aggregate_job", "prio3_leader_finish_job",
+                 "prio3_leader_upload_job"):
         getattr(L, name + "_submit").argtypes = getattr(L, name).argtypes + [C.c_int, P(vp)]
     L.prio3_leader_prepare_init_batch_submit.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, P(vp),
                                                          C.c_int, P(vp)]
@@ -1410,6 +1440,67 @@ class HelperEngine:
         if rc:
             raise RuntimeError(f"prio3_leader_upload_batch failed (rc={rc})")
         return out
+
+    def submit_leader_upload_job(self, reports, report_len, task_id: bytes, now: int,
+                                 report_deadline: int, task_opener=None, task_config_id: int = 0,
+                                 global_opener=None, global_config_id: int = 0,
+                                 task_expiration: int = UINT64_MAX,
+                                 report_expiry_age: int = UINT64_MAX, ext_stride: int = 64,
+                                 helper_enc_len: int = 32, helper_ct_stride: int = 0,
+                                 notify_fd=None) -> Ticket:
+        """``leader_upload_job`` as a ticket (prio3_leader_upload_job_submit): the rows and
+        lengths are consumed when this returns, ``wait()`` returns the blocking method's dict."""
+        return self.leader_upload_job(reports, report_len, task_id, now, report_deadline,
+                                      task_opener, task_config_id, global_opener,
+                                      global_config_id, task_expiration, report_expiry_age,
+                                      ext_stride, helper_enc_len, helper_ct_stride, _ticket=True,
+                                      _notify_fd=notify_fd)
+
+    def leader_upload_job(self, reports, report_len, task_id: bytes, now: int,
+                          report_deadline: int, task_opener=None, task_config_id: int = 0,
+                          global_opener=None, global_config_id: int = 0,
+                          task_expiration: int = UINT64_MAX, report_expiry_age: int = UINT64_MAX,
+                          ext_stride: int = 64, helper_enc_len: int = 32,
+                          helper_ct_stride: int = 0, _ticket=False, _notify_fd=None) -> dict:
+        """``leader_upload_batch`` through the upload executor (prio3_leader_upload_job): the
+        same arguments and the same dict, byte for byte; concurrent jobs of every task that
+        opens with the same keypairs share one launch chain."""
+        rows = np.ascontiguousarray(reports, np.uint8)
+        ln = np.ascontiguousarray(report_len, np.uint32)
+        if rows.ndim != 2 or ln.shape != (rows.shape[0],):
+            raise ValueError("reports must be [n, report_stride] and report_len [n]")
+        n, stride = rows.shape
+        ho, hc, go, gc = self._upload_args(task_opener, global_opener, task_config_id,
+                                           global_config_id, task_id, stride, ext_stride)
+        sz = self.sz
+        out = dict(report_ids=np.zeros((n, 16), np.uint8), times=np.zeros(n, np.uint64),
+                   public_shares=np.zeros((n, sz.public_share_len), np.uint8),
+                   leader_input_shares=np.zeros((n, sz.leader_input_share_len), np.uint8),
+                   extensions=np.zeros((n, ext_stride), np.uint8), ext_len=np.zeros(n, np.uint32),
+                   helper_config_ids=np.zeros(n, np.uint8),
+                   helper_enc=np.zeros((n, helper_enc_len), np.uint8),
+                   helper_ct=np.zeros((n, helper_ct_stride), np.uint8),
+                   helper_ct_len=np.zeros(n, np.uint32), leader_config_ids=np.zeros(n, np.uint8),
+                   status=np.zeros(n, np.uint8))
+        a = lambda x: x.ctypes.data if x.size else None  # noqa: E731
+        h = lambda o: None if o is None else o.value  # noqa: E731
+        jin = Prio3UploadJobIn(
+            task_opener=h(ho), global_opener=h(go), task_config_id=hc, global_config_id=gc, n=n,
+            task_id=(C.c_uint8 * 32).from_buffer_copy(bytes(task_id)), now=int(now),
+            report_deadline=int(report_deadline), task_expiration=int(task_expiration),
+            report_expiry_age=int(report_expiry_age), reports=a(rows), report_len=a(ln),
+            report_stride=stride, ext_stride=ext_stride, helper_enc_len=helper_enc_len,
+            helper_ct_stride=helper_ct_stride)
+        jout = Prio3UploadJobOut(**{k: a(v) for k, v in out.items()})
+        name = "prio3_leader_upload_job"
+        try:
+            return _job_call(name, (self.handle, C.byref(jin), C.byref(jout)),
+                             [self, task_opener, global_opener, rows, ln], list(out.values()),
+                             lambda: out, _ticket, _notify_fd)
+        except RuntimeError as e:
+            if "(rc=-3)" in str(e):
+                raise NotImplementedError(f"{name}: unsupported instance") from None
+            raise
 
     def leader_upload_device(self, reports, report_len, task_id: bytes, now: int,
                              report_deadline: int, task_opener=None, task_config_id: int = 0,
